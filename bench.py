@@ -1,7 +1,7 @@
 """Benchmark: K3M tri-modal pretraining step (bert_base_6layer_6conect) on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}] [--dtype fp32|bf16]
-                    [--batch B] [--no-cpu-baseline]
+                    [--batch B] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
 
 One step = forward + backward + (RCCL gradient all-reduce when N > 1) + AdamW + LR schedule over
 one synthetic batch resident in HBM (SURVEY.md §8(d) input spec: random token ids, region
@@ -15,7 +15,18 @@ itself, before touching the GPU, and exits with its status.  Each rank runs its 
 (weak scaling, global batch = B N); the timed region is bracketed by barrier + synchronize and the
 max over ranks is taken.
 
-Rank 0 prints ONE JSON line with the driver's contract plus
+A plain run sets up, runs the W warm-up steps, times the K steps, writes the last timed step's outputs with
+``--dump-outputs DIR`` (DIR/<name>.npy, float32: what Trainer.step returned, i.e. the losses, the pooled outputs and
+the structure-aggregation states; the batch, the initial weights and the dropout seeds are seeded, so two runs with
+the same arguments see identical inputs.  The default backward sums embedding, structure and LPM gradients through
+float atomics, whose run-to-run order the training steps amplify to ~1e-3 of the loss after 13 steps, so a run with
+``--dump-outputs`` switches the step to the deterministic mode (the fixed-order forms of those four
+backward kernels, everything else unchanged): its steps, the timed ones included, are bit-identical from run to run
+and ~5 % slower, and the line says ``"deterministic": true``) and prints ONE JSON line (rank 0): the driver's
+contract (metric, value, unit, higher_is_better, dtype, ms_per_step) with the workload, the host
+issue time of the timed steps, the graph decision, the last loss and the all-reduce figures of a multi-rank run.  ``--full`` adds, from runs of their own
+around the timed steps,
+  host_issue_ms   — the host time to issue one step from an idle GPU (two extra untimed steps);
   roofline        — the dominant kernel by time (the 256x256 weight-gradient walk, ~21 % of the fp32 step) on its
                     largest launch shape, the text-layer FFN1 weight gradient (3072 x 768 x 2BT+2BP rows),
                     timed with HIP events on its stream over the timed steps, against the peak of the
@@ -27,7 +38,8 @@ Rank 0 prints ONE JSON line with the driver's contract plus
                     FFNs, LayerNorms; forward + backward) timed with HIP events: their algorithmic
                     FLOPs / time against the same peak (north-star target >= 0.40);
   cpu_baseline    — the CPU oracle (plain PyTorch fp32 restatement of the same step, oracle/) on the
-                    host cores, bounded sample (rank 0, N = 1 only).
+                    host cores, bounded sample (rank 0, N = 1 only; ``--no-cpu-baseline`` leaves it and parity out);
+  gemm_all        — every GEMM launch of one eager step after the timed region.
 """
 import argparse
 import json
@@ -82,7 +94,13 @@ def parse():
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default: the config's)")
     ap.add_argument("--dtype", default=None, choices=["fp32", "bf16"], help="default: the config's")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: the "
+                    "HIP-event probes (roofline, roofline_ffn1, coattn, gemm_all), host_issue_ms, the parity check "
+                    "and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the outputs of the last timed step "
+                    "as DIR/<name>.npy (float32; rank 0); the whole run uses the deterministic mode (bit-identical "
+                    "run to run, ~5 %% slower)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline and parity")
     ap.add_argument("--cpu-batch", type=int, default=64, help="CPU baseline batch (the GPU workload's bs=64)")
     ap.add_argument("--cpu-steps", type=int, default=1, help="timed CPU steps at --cpu-batch (after a bs=8 "
                     "warm-up step and a bs=8 sample of 2 timed steps)")
@@ -443,6 +461,37 @@ def cpu_baseline(cfg, shape, bsz, steps, gpu_losses=None, bar=1e-3):
     return res, parity
 
 
+DUMP_LIMIT = 64 * 1000 * 1000   # bytes over all dumped arrays
+
+
+def snapshot_outputs(out):
+    """Host copies of a step's output tensors (a graph replay's larger outputs are overwritten by the next replay)."""
+    import torch
+    snap = {}
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            v = v.detach()
+            snap[k] = v.to(torch.float64 if v.dtype == torch.float64 else torch.float32).cpu().numpy()
+    return snap
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT):
+    """DIR/<name>.npy per output.  When everything together exceeds ``limit`` bytes each array gets an equal share and
+    a larger one is written as a fixed sample: its flat elements at sorted indices drawn without replacement by
+    numpy's RandomState(0) (the same indices in every run of the same shapes)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = None
+    if sum(a.nbytes for a in arrays.values()) > limit:
+        share = limit // max(1, len(arrays))
+    for name in sorted(arrays):
+        a = arrays[name]
+        if share is not None and a.nbytes > share:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -471,6 +520,9 @@ def main():
         else:
             dist.init_process_group(args.backend)
         from k3m_amd.ddp import GradAllReducer
+    from k3m_amd import ops
+    if args.dump_outputs:   # every rank: outputs that two runs (and two builds) can be compared on, bit for bit
+        ops.set_deterministic(True)
     from k3m_amd.config import pretrain_config
     from k3m_amd.trainer import Trainer
     from k3m_amd.synthetic import synthetic_batch
@@ -491,15 +543,16 @@ def main():
     rows = 2 * B * T + 2 * B * P   # the wide text buffer
     H, I = cfg.hidden_size, cfg.intermediate_size
     probe = GemmProbe(rows, I, H)   # FFN1 forward
-    probe.install()
     # the dominant kernel by time: the weight-gradient walk; its launches of the text-layer weight gradients
     # (gW[n_out, n_in] += dY^T X over the 20,992 wide rows; FFN1's 3072 x 768 x 20,992 is the largest shape)
     wprobe = GemmProbe(I, H, rows, more=[(H, I, rows), (3 * H, H, rows), (H, H, rows)])
-    wprobe.install()
     cprobe = CoattnProbe()
-    cprobe.install()
     gall = GemmAllProbe()
-    gall.install()
+    if args.full:   # a plain run leaves the engine's entry points unwrapped
+        probe.install()
+        wprobe.install()
+        cprobe.install()
+        gall.install()
 
     def barrier():
         if use_dist:
@@ -512,10 +565,10 @@ def main():
     for _ in range(warm):
         tr.step(batch)
     barrier()
-    # host issue cost from an idle GPU (the timed loop's host time includes blocking on a full launch queue): two
-    # more untimed steps before the timed region (so a profile's last steps are the timed ones)
+    # --full: host issue cost from an idle GPU (the timed loop's host time includes blocking on a full launch queue):
+    # two more untimed steps before the timed region (so a profile's last steps are the timed ones)
     issue = []
-    for _ in range(2):
+    for _ in range(2 if args.full else 0):
         torch.cuda.synchronize()
         h0 = time.perf_counter()
         tr.step(batch)
@@ -525,7 +578,7 @@ def main():
     # step is issued eagerly; with graph replay (a captured launch cannot be bracketed by timing events) they
     # run in PROBE_STEPS eager steps right after it (same kernels, same shapes)
     graphed = tr.graph and tr._graphs is not None and tr._graphs.graph is not None
-    probe.active = wprobe.active = cprobe.active = not graphed
+    probe.active = wprobe.active = cprobe.active = args.full and not graphed
     t0 = time.perf_counter()
     host = 0.0
     for _ in range(args.steps):
@@ -536,6 +589,7 @@ def main():
     dt = time.perf_counter() - t0
     loss = float(out["loss"])   # the last timed step's (a replay's outputs are overwritten by the next)
     probe.active = wprobe.active = cprobe.active = False
+    dumped = snapshot_outputs(out) if (args.dump_outputs and rank == 0) else None
     per_rank = [dt]
     if use_dist:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -544,7 +598,7 @@ def main():
         per_rank = [float(x) for x in gl]
         dt = max(per_rank)
     probe_steps = args.steps
-    if graphed:
+    if graphed and args.full:
         probe_steps = PROBE_STEPS
         mode, tr.graph = tr.graph, False
         probe.active = wprobe.active = cprobe.active = True
@@ -553,14 +607,17 @@ def main():
         barrier()
         probe.active = wprobe.active = cprobe.active = False
         tr.graph = mode
-    # every GEMM of one eager step, after the timed region (the per-launch events would perturb the timed steps)
-    mode, tr.graph = tr.graph, False
-    gall.active = True
-    tr.step(batch)
-    barrier()
-    gall.active = False
-    tr.graph = mode
+    if args.full:
+        # every GEMM of one eager step, after the timed region (the per-launch events would perturb the timed steps)
+        mode, tr.graph = tr.graph, False
+        gall.active = True
+        tr.step(batch)
+        barrier()
+        gall.active = False
+        tr.graph = mode
     tr.finish()
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped)
     ms_step = 1000.0 * dt / args.steps
     value = world * B * args.steps / dt
     gemm_ms = probe.mean_ms()
@@ -598,51 +655,57 @@ def main():
         # host time to issue one step (Python engine + launches; the GPU runs behind it): when this
         # approaches ms_per_step the step is launch-bound and the GPU idles between kernels
         "host_ms_per_step": round(1000.0 * host / args.steps, 3),
-        # the same, each step issued from an idle GPU (two extra untimed steps): the Python engine's own cost
-        "host_issue_ms": round(1000.0 * min(issue), 3),
         # the step's issue mode: K3M_GRAPH auto replays a hipGraph when the eager issue time is a large share of
         # the GPU time (decision: the measured eager step); captures / replays count graph launches
         "graph": ({"captures": tr._graphs.captures, "replays": tr._graphs.replays,
                    "decision": tr._graphs.last_decision} if tr._graphs is not None else None),
         "loss": round(loss, 4),
+        # fixed-order backward sums (K3M_DETERMINISTIC=1, or switched on by --dump-outputs)
+        "deterministic": bool(ops.DETERMINISTIC),
         "step_mfma_frac_vs_ref_flops": round(B * ref_sample / (ms_step * 1e-3) / peak, 4),
-        # the dominant kernel by time (profiles/r5e/cfg2/step_split.txt: the 256x256 weight-gradient walk, 21 % of the
-        # fp32 step; the bf16 step's largest class likewise), measured on its largest launch shape: the FFN1 weight
-        # gradient, 12 launches per step
-        "roofline": {"bound": "mfma", "kernel": "%s, FFN1 weight gradient %dx%dx%d (split-K, tn)" % (wkname, Mw, Nw, Kw),
-                     "achieved": round(w_ach / 1e12, 2) if w_ach else None,
-                     "peak": peak / 1e12, "unit": "TFLOP/s",
-                     "frac": round(w_ach / peak, 4) if w_ach else None,
-                     "traffic": w_traffic,
-                     "avg_launch_ms": round(w_ms, 4) if w_ms else None,
-                     "launches": len(wprobe.launches(wprobe.key)),
-                     "probe": "HIP events, %s" % ("%d eager steps after the timed graph replays" % probe_steps if graphed
-                                                  else "timed region"),
-                     "algorithmic_flops_per_launch": w_flops,
-                     "peak_basis": ("bf16 dense MFMA" if bf else "fp32 via 6 bf16 MFMA partial products = bf16 dense "
-                                    "peak / 6" if x6 else "f32 MFMA"),
-                     "traffic_unit": "HBM bytes/launch (rocprofv3 PMC, %s)" % w_traffic_src if w_traffic else None,
-                     # every text-layer weight gradient on this kernel (QKV, attention output, FFN1, FFN2 x 12 layers)
-                     "class": {"launches": nw, "ms_per_step": round(w_tot_ms / probe_steps, 3) if nw else None,
-                               "achieved": round(w_tot_flops / (w_tot_ms * 1e-3) / 1e12, 2) if nw else None,
-                               "frac": round(w_tot_flops / (w_tot_ms * 1e-3) / peak, 4) if nw else None}},
-        # the FFN1 forward (bias + GELU epilogue), the roofline line of rounds 1-5
-        "roofline_ffn1": {"bound": "mfma", "kernel": "%s text-layer FFN1 %dx%dx%d" % (kname, Mg, Ng, Kg),
-                          "achieved": round(achieved / 1e12, 2) if achieved else None,
-                          "peak": peak / 1e12, "unit": "TFLOP/s",
-                          "frac": round(achieved / peak, 4) if achieved else None,
-                          "traffic": traffic,
-                          "avg_launch_ms": round(gemm_ms, 4) if gemm_ms else None,
-                          "launches": len(probe.launches(probe.key)),
-                          "algorithmic_flops_per_launch": gemm_flops,
-                          "traffic_unit": "HBM bytes/launch (rocprofv3 PMC, %s)" % traffic_src if traffic else None},
-        "gemm_all": gall.summary(peak),
-        "coattn": {"ms_per_step": round(co_ms, 3) if co_ms else None,
-                   "algorithmic_tflop_per_step": round(co_flops / 1e12, 3),
-                   "achieved": round(co_flops / (co_ms * 1e-3) / 1e12, 2) if co_ms else None,
-                   "frac": round(co_flops / (co_ms * 1e-3) / peak, 4) if co_ms else None,
-                   "scope": "18 co-attention layers fwd+bwd (lock-step blocks incl. attention and LayerNorm)"},
     }
+    if args.full:
+        res.update({
+            # the host time to issue one step, each issued from an idle GPU (two extra untimed steps): the Python
+            # engine's own cost
+            "host_issue_ms": round(1000.0 * min(issue), 3),
+            # the dominant kernel by time (profiles/r5e/cfg2/step_split.txt: the 256x256 weight-gradient walk, 21 % of the
+            # fp32 step; the bf16 step's largest class likewise), measured on its largest launch shape: the FFN1 weight
+            # gradient, 12 launches per step
+            "roofline": {"bound": "mfma", "kernel": "%s, FFN1 weight gradient %dx%dx%d (split-K, tn)" % (wkname, Mw, Nw, Kw),
+                         "achieved": round(w_ach / 1e12, 2) if w_ach else None,
+                         "peak": peak / 1e12, "unit": "TFLOP/s",
+                         "frac": round(w_ach / peak, 4) if w_ach else None,
+                         "traffic": w_traffic,
+                         "avg_launch_ms": round(w_ms, 4) if w_ms else None,
+                         "launches": len(wprobe.launches(wprobe.key)),
+                         "probe": "HIP events, %s" % ("%d eager steps after the timed graph replays" % probe_steps if graphed
+                                                      else "timed region"),
+                         "algorithmic_flops_per_launch": w_flops,
+                         "peak_basis": ("bf16 dense MFMA" if bf else "fp32 via 6 bf16 MFMA partial products = bf16 dense "
+                                        "peak / 6" if x6 else "f32 MFMA"),
+                         "traffic_unit": "HBM bytes/launch (rocprofv3 PMC, %s)" % w_traffic_src if w_traffic else None,
+                         # every text-layer weight gradient on this kernel (QKV, attention output, FFN1, FFN2 x 12 layers)
+                         "class": {"launches": nw, "ms_per_step": round(w_tot_ms / probe_steps, 3) if nw else None,
+                                   "achieved": round(w_tot_flops / (w_tot_ms * 1e-3) / 1e12, 2) if nw else None,
+                                   "frac": round(w_tot_flops / (w_tot_ms * 1e-3) / peak, 4) if nw else None}},
+            # the FFN1 forward (bias + GELU epilogue), the roofline line of rounds 1-5
+            "roofline_ffn1": {"bound": "mfma", "kernel": "%s text-layer FFN1 %dx%dx%d" % (kname, Mg, Ng, Kg),
+                              "achieved": round(achieved / 1e12, 2) if achieved else None,
+                              "peak": peak / 1e12, "unit": "TFLOP/s",
+                              "frac": round(achieved / peak, 4) if achieved else None,
+                              "traffic": traffic,
+                              "avg_launch_ms": round(gemm_ms, 4) if gemm_ms else None,
+                              "launches": len(probe.launches(probe.key)),
+                              "algorithmic_flops_per_launch": gemm_flops,
+                              "traffic_unit": "HBM bytes/launch (rocprofv3 PMC, %s)" % traffic_src if traffic else None},
+            "gemm_all": gall.summary(peak),
+            "coattn": {"ms_per_step": round(co_ms, 3) if co_ms else None,
+                       "algorithmic_tflop_per_step": round(co_flops / 1e12, 3),
+                       "achieved": round(co_flops / (co_ms * 1e-3) / 1e12, 2) if co_ms else None,
+                       "frac": round(co_flops / (co_ms * 1e-3) / peak, 4) if co_ms else None,
+                       "scope": "18 co-attention layers fwd+bwd (lock-step blocks incl. attention and LayerNorm)"},
+        })
     if use_dist:
         res["per_rank_s"] = [round(x, 4) for x in per_rank]
         res["backend"] = args.backend
@@ -657,7 +720,7 @@ def main():
             res["allreduce_dtype"] = tm["comm_dtype"]
             res["grad_bytes_per_rank"] = int(sum(b - a for blk in tr.ddp.blocks.values() for a, b in blk) *
                                              (2 if tm["comm_dtype"] == "bf16" else 4))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             gl = gpu_parity_losses(tr, cfg, shape, args.cpu_batch)
         except Exception as e:  # noqa: BLE001 - reported, never masks the GPU result

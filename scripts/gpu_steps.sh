@@ -28,7 +28,7 @@ for s in "$@"; do
     bench4) step bench4 900 python bench.py --config 4 --steps 5 --warmup 2 --no-cpu-baseline ;;
     bench5) step bench5 900 python bench.py --config 5 --steps 5 --warmup 2 --no-cpu-baseline ;;
     spawn2) step spawn2 600 python bench.py --gpus 2 --steps 3 --warmup 1 --backend gloo --batch 16 ;;
-    bench) step bench 600 python bench.py --steps 10 --warmup 3 ;;
+    bench) step bench 600 python bench.py --full --steps 10 --warmup 3 ;;
     benchq) step bench 600 python bench.py --steps 5 --warmup 2 --no-cpu-baseline ;;
     profbf) export TMPDIR=/tmp; step profbf 900 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/profbf -o run -- python bench.py --config 3 --steps 3 --warmup 1 --no-cpu-baseline ;;
     profbf10) export TMPDIR=/tmp; step profbf10 900 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/profbf10 -o run -- python bench.py --config 3 --steps 10 --warmup 2 --no-cpu-baseline ;;
