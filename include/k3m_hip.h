@@ -242,6 +242,19 @@ int k3m_relu_split3_bwd(const void* dc, const void* c, void* dx0, void* dx1, voi
 int k3m_mean3(const void* x0, const void* x1, const void* x2, void* out, long long n, int dtype, hipStream_t stream);
 int k3m_mean3_bwd(const void* dout, void* dx0, void* dx1, void* dx2, long long n, int accumulate, int dtype,
                   hipStream_t stream);
+/* if_pre_sampling == 2 (soft gate, vilbert_k3m.py:2300-2329): z = c * a over [rows, 3D]; c in `dtype`, a fp32
+ * (the sigmoid scores), z in `z_dtype` (the operand dtype of the soft_* GEMM that follows).
+ * backward: dc = dz * a ; dpre = dz * c * a * (1 - a) in fp32 and, if dpre_bf16 != NULL, also rounded to bf16
+ * (the gate GEMMs' operand copy).  Vector accesses: D % 4 == 0 and operands on a 4-element boundary,
+ * K3M_EINVAL otherwise.                                                                          */
+int k3m_soft_scale(const void* c, const float* a, void* z, int rows, int d, int dtype, int z_dtype,
+                   hipStream_t stream);
+int k3m_soft_scale_bwd(const void* dz, const void* c, const float* a, void* dc, float* dpre, void* dpre_bf16, int rows,
+                       int d, int dtype, hipStream_t stream);
+/* if_pre_sampling == 3: out = (x1+x2)/2 ; backward: dx_k (+)= dout/2 (either dx_k may be NULL).  n % 4 == 0. */
+int k3m_mean2(const void* x1, const void* x2, void* out, long long n, int dtype, hipStream_t stream);
+int k3m_mean2_bwd(const void* dout, void* dx1, void* dx2, long long n, int accumulate, int dtype,
+                  hipStream_t stream);
 /* out[s, :] (+)= scale * mean(x[s, start:len, :])  (pooled outputs :2405-2409) and backward. */
 int k3m_seq_mean(const void* x, int nseq, int len, int start, int d, float scale, float* out, int accumulate,
                  int dtype, hipStream_t stream);

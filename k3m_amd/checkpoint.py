@@ -20,7 +20,7 @@ Files are read with ``torch.load(weights_only=True)`` (tensors and plain contain
 """
 import torch
 
-from .params import is_frozen, is_no_decay
+from .params import frozen_of, is_no_decay
 
 DECODER_KEY = "cls.predictions.decoder.weight"
 TIED_TO = "embeddings.word_embeddings.weight"
@@ -89,10 +89,11 @@ def optimizer_state_dict(fp, m, v, step, groups, group_lr, base_lr, betas=(0.9, 
     ``bias_correction=False``).  The --fp16 branch wraps FusedAdam in FP16_Optimizer, whose own
     state_dict (fp32 master copies, loss scaler) is not reproduced."""
     state, pg, idx = {}, [], 0
+    frozen = frozen_of(fp)
     for gi, (gnames, wd, mult) in enumerate(groups):
         ids = []
         for n in gnames:
-            if step > 0 and not is_frozen(n):
+            if step > 0 and n not in frozen:
                 o, k = fp.offsets[n], fp.p[n].numel()
                 st = {"exp_avg": m[o:o + k].view(fp.shapes[n]).to("cpu", copy=True),
                       "exp_avg_sq": v[o:o + k].view(fp.shapes[n]).to("cpu", copy=True)}
@@ -128,6 +129,7 @@ def load_optimizer_state_dict(fp, m, v, osd, groups):
         for pid, n in zip(g["params"], gnames):
             pid_name[pid] = n
     step = 0
+    frozen = frozen_of(fp)
     with torch.no_grad():
         m.zero_()
         v.zero_()
@@ -139,7 +141,7 @@ def load_optimizer_state_dict(fp, m, v, osd, groups):
                 if not st:
                     continue
                 n = pid_name[pid]
-                if is_frozen(n):
+                if n in frozen:
                     continue
                 o, k = fp.offsets[n], fp.p[n].numel()
                 if tuple(st["exp_avg"].shape) != tuple(fp.shapes[n]):

@@ -140,6 +140,103 @@ __global__ void seq_mean_bwd_kernel(const float* dout, int nseq, int len, int st
 
 int grid_for(long long n) { return (int)std::min<long long>((n + 255) / 256, 8192); }
 
+// ---- soft gate (if_pre_sampling == 2) and interactive-only mean (== 3): streaming kernels, four
+// elements per lane per trip (one 16-byte fp32 access, one 8-byte packed bf16 access), no atomics.
+__device__ __forceinline__ void ld4(const float* p, float (&v)[4]) {
+  const floatx4 t = *reinterpret_cast<const floatx4*>(p);
+  v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+}
+__device__ __forceinline__ void ld4(const bf16_t* p, float (&v)[4]) {
+  const uint2 t = *reinterpret_cast<const uint2*>(p);
+  v[0] = __uint_as_float(t.x << 16);
+  v[1] = __uint_as_float(t.x & 0xffff0000u);
+  v[2] = __uint_as_float(t.y << 16);
+  v[3] = __uint_as_float(t.y & 0xffff0000u);
+}
+__device__ __forceinline__ void st4(float* p, const float (&v)[4]) {
+  floatx4 t;
+  t[0] = v[0]; t[1] = v[1]; t[2] = v[2]; t[3] = v[3];
+  *reinterpret_cast<floatx4*>(p) = t;
+}
+__device__ __forceinline__ void st4(bf16_t* p, const float (&v)[4]) {
+  uint2 t;
+  t.x = (uint32_t)from_f<bf16_t>(v[0]).x | ((uint32_t)from_f<bf16_t>(v[1]).x << 16);
+  t.y = (uint32_t)from_f<bf16_t>(v[2]).x | ((uint32_t)from_f<bf16_t>(v[3]).x << 16);
+  *reinterpret_cast<uint2*>(p) = t;
+}
+
+// z = c * a ; n4 = element count / 4
+template <typename T, typename Z>
+__global__ void soft_scale_kernel(const T* c, const float* a, Z* z, long long n4) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    float cv[4], av[4], zv[4];
+    ld4(c + 4 * i, cv);
+    ld4(a + 4 * i, av);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) zv[k] = cv[k] * av[k];
+    st4(z + 4 * i, zv);
+  }
+}
+
+// dc = dz * a ; dpre = dz * c * a * (1 - a), fp32 and (dpre16 != NULL) its bf16 rounding
+template <typename T>
+__global__ void soft_scale_bwd_kernel(const T* dz, const T* c, const float* a, T* dc, float* dpre, bf16_t* dpre16,
+                                      long long n4) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    float gv[4], cv[4], av[4], dcv[4], dp[4];
+    ld4(dz + 4 * i, gv);
+    ld4(c + 4 * i, cv);
+    ld4(a + 4 * i, av);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      dcv[k] = gv[k] * av[k];
+      dp[k] = gv[k] * cv[k] * av[k] * (1.f - av[k]);
+    }
+    st4(dc + 4 * i, dcv);
+    st4(dpre + 4 * i, dp);
+    if (dpre16) st4(dpre16 + 4 * i, dp);
+  }
+}
+
+template <typename T>
+__global__ void mean2_kernel(const T* x1, const T* x2, T* out, long long n4) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    float u[4], v[4], o[4];
+    ld4(x1 + 4 * i, u);
+    ld4(x2 + 4 * i, v);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = (u[k] + v[k]) * 0.5f;
+    st4(out + 4 * i, o);
+  }
+}
+template <typename T>
+__global__ void mean2_bwd_kernel(const T* dout, T* dx1, T* dx2, long long n4, int acc) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    float g[4];
+    ld4(dout + 4 * i, g);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) g[k] *= 0.5f;
+    T* dx[2] = {dx1, dx2};
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      if (!dx[q]) continue;
+      float o[4];
+      if (acc) {
+        ld4(dx[q] + 4 * i, o);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] += g[k];
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = g[k];
+      }
+      st4(dx[q] + 4 * i, o);
+    }
+  }
+}
+
+// the vector accesses need the operand on a 4-element boundary of its type (NULL passes)
+bool al4(const void* p, int dtype) { return ((uintptr_t)p & (dtype == K3M_BF16 ? 7u : 15u)) == 0; }
+
 }  // namespace
 
 #define DISPATCH_T(dtype, ...)      \
@@ -213,6 +310,58 @@ extern "C" int k3m_mean3_bwd(const void* dout, void* dx0, void* dx1, void* dx2, 
   if (n == 0) return 0;
   DISPATCH_T(dtype, hipLaunchKernelGGL(mean3_bwd_kernel<T>, dim3(grid_for(n)), dim3(256), 0, st, (const T*)dout,
                                        (T*)dx0, (T*)dx1, (T*)dx2, n, accumulate));
+  K3M_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int k3m_soft_scale(const void* c, const float* a, void* z, int rows, int d, int dtype, int z_dtype,
+                              hipStream_t st) {
+  K3M_ARG(c && a && z && rows >= 0 && d >= 0 && d % 4 == 0);
+  K3M_ARG(z_dtype == K3M_F32 || z_dtype == K3M_BF16);
+  K3M_ARG(al4(c, dtype) && al4(a, K3M_F32) && al4(z, z_dtype));
+  const long long n4 = (long long)rows * 3 * d / 4;
+  if (n4 == 0) return 0;
+  if (z_dtype == K3M_F32) {
+    DISPATCH_T(dtype, hipLaunchKernelGGL((soft_scale_kernel<T, float>), dim3(grid_for(n4)), dim3(256), 0, st,
+                                         (const T*)c, a, (float*)z, n4));
+  } else {
+    DISPATCH_T(dtype, hipLaunchKernelGGL((soft_scale_kernel<T, bf16_t>), dim3(grid_for(n4)), dim3(256), 0, st,
+                                         (const T*)c, a, (bf16_t*)z, n4));
+  }
+  K3M_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int k3m_soft_scale_bwd(const void* dz, const void* c, const float* a, void* dc, float* dpre, void* dpre_bf16,
+                                  int rows, int d, int dtype, hipStream_t st) {
+  K3M_ARG(dz && c && a && dc && dpre && rows >= 0 && d >= 0 && d % 4 == 0);
+  K3M_ARG(al4(dz, dtype) && al4(c, dtype) && al4(a, K3M_F32) && al4(dc, dtype) && al4(dpre, K3M_F32) &&
+          al4(dpre_bf16, K3M_BF16));
+  const long long n4 = (long long)rows * 3 * d / 4;
+  if (n4 == 0) return 0;
+  DISPATCH_T(dtype, hipLaunchKernelGGL(soft_scale_bwd_kernel<T>, dim3(grid_for(n4)), dim3(256), 0, st, (const T*)dz,
+                                       (const T*)c, a, (T*)dc, dpre, (bf16_t*)dpre_bf16, n4));
+  K3M_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int k3m_mean2(const void* x1, const void* x2, void* out, long long n, int dtype, hipStream_t st) {
+  K3M_ARG(x1 && x2 && out && n >= 0 && n % 4 == 0);
+  K3M_ARG(al4(x1, dtype) && al4(x2, dtype) && al4(out, dtype));
+  if (n == 0) return 0;
+  DISPATCH_T(dtype, hipLaunchKernelGGL(mean2_kernel<T>, dim3(grid_for(n / 4)), dim3(256), 0, st, (const T*)x1,
+                                       (const T*)x2, (T*)out, n / 4));
+  K3M_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int k3m_mean2_bwd(const void* dout, void* dx1, void* dx2, long long n, int accumulate, int dtype,
+                             hipStream_t st) {
+  K3M_ARG(dout && n >= 0 && n % 4 == 0);
+  K3M_ARG(al4(dout, dtype) && al4(dx1, dtype) && al4(dx2, dtype));
+  if (n == 0) return 0;
+  DISPATCH_T(dtype, hipLaunchKernelGGL(mean2_bwd_kernel<T>, dim3(grid_for(n / 4)), dim3(256), 0, st, (const T*)dout,
+                                       (T*)dx1, (T*)dx2, n / 4, accumulate));
   K3M_CHECK_LAUNCH();
   return 0;
 }

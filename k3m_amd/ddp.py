@@ -9,7 +9,8 @@ MI355X:
   aggregator first, then each encoder block (text layer, image layer, co-attention block) as soon
   as its backward finishes, embeddings last (the word embedding also carries the tied MLM
   decoder gradient, so it is final only at the very end);
-* the 86 never-grad tensors (frozen segment) are excluded — apex/torch DDP would wait on them;
+* the never-grad tensors of the fusion mode (frozen segment: 86 by default, params.is_frozen) are excluded —
+  apex/torch DDP would wait on them;
 * all-reduces run on a dedicated HIP stream that waits on an event recorded after the block's
   backward, so RCCL traffic overlaps the remaining backward kernels; averaging (1/world) is
   folded into the AdamW kernel's grad_scale;
@@ -30,7 +31,7 @@ import collections
 import torch
 import torch.distributed as dist
 
-from .params import param_spec, segment_of
+from .params import frozen_of, param_spec
 
 
 def _block_of(name):
@@ -56,8 +57,9 @@ class GradAllReducer(object):
         self.fp = fp
         # contiguous ranges per readiness block
         ranges = {}
+        frozen = frozen_of(fp)
         for name, shape in fp.spec:
-            if segment_of(name) == "frozen":
+            if name in frozen:
                 continue
             blk = _block_of(name)
             o = fp.offsets[name]

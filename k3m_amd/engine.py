@@ -32,7 +32,7 @@ import torch
 from . import debug
 from . import _lib as L
 from . import ops
-from .params import flat_layout
+from .params import flat_layout, frozen_names
 
 EPS = 1e-12
 
@@ -58,6 +58,7 @@ class FlatParams(object):
 
     def __init__(self, cfg, device, bf16_shadow=False):
         self.spec, self.offsets, self.segments, self.total, self.shapes = flat_layout(cfg)
+        self.frozen = frozen_names(cfg)   # the never-grad tensors of cfg's fusion mode (the frozen segment)
         self.device = device
         self.data = torch.zeros(self.total, dtype=torch.float32, device=device)
         self.grad = torch.zeros(self.total, dtype=torch.float32, device=device)
@@ -533,6 +534,7 @@ class K3MEngine(object):
         self.vemb_ln = LN(fp, "v_embeddings.LayerNorm")
         self.gate = {m: Lin(fp, ["score_self_%s" % m, "score_cross1_%s" % m, "score_cross2_%s" % m])
                      for m in ("v", "t", "pv")}
+        self.soft = {m: Lin(fp, "soft_%s" % m) for m in ("v", "t", "pv")}   # if_pre_sampling == 2 only
         self.map_b2i = Lin(fp, "map_bi_to_individual")
         # "pretrain": the pretraining heads + LPM; "item_alignment": the encoder up to c_final only
         # (K3MForItemAlignment.item_embedding, vilbert_k3m.py:3329-3377; its pair head is k3m_amd.finetune)
@@ -602,7 +604,8 @@ class K3MEngine(object):
         """Runs the forward of the step; returns (losses dict of device tensors, ctx for backward).
 
         batch: dict of device tensors with the reference names (A0 in SURVEY.md §8(a)).
-        noise: optional {v,t,pv: [B, L, 3, D]} gumbel noise; ent_neg/val_neg optional [B,NPV,2].
+        noise: optional {v,t,pv: [B, L, 3, D]} gumbel noise (used by the hard gate, if_pre_sampling 1, only);
+        ent_neg/val_neg optional [B,NPV,2].
         groups: the batch is that many independent model calls stacked along dim 0 (the item
         alignment pair: item 1 rows then item 2 rows); only the structure aggregator's
         zero-triple fallback crosses items, and it is kept inside each group."""
@@ -748,7 +751,9 @@ class K3MEngine(object):
         }
         fus = {}
         gate_a = {}
-        if mode == 1:   # the three modalities' gate GEMMs are independent: one grouped launch (GROUP_GATE)
+        if mode not in (0, 1, 2, 3):
+            raise NotImplementedError("if_pre_sampling=%s" % mode)
+        if mode in (1, 2):   # the three modalities' gate GEMMs are independent: one grouped launch (GROUP_GATE)
             ccs = {}
             for m in ("v", "t", "pv"):
                 x0, x1, x2, out, D = streams[m]
@@ -760,7 +765,20 @@ class K3MEngine(object):
             with (ops.grouped() if GROUP_GATE else contextlib.nullcontext()):
                 for m in ("v", "t", "pv"):
                     gate_a[m] = self.gate[m].fwd(ccs[m][1], epi=L.EPI_BIAS_SIGMOID, out_dtype=torch.float32)
-        for m in ("v", "t", "pv"):
+        if mode == 2:
+            # soft gate (:2300-2329): out = soft_m(c * sigmoid(scores)), no gumbel draw.  z is written in the
+            # soft GEMMs' operand dtype (bf16 directly in bf16 mode); the three GEMMs are one grouped launch.
+            for m in ("v", "t", "pv"):
+                cc, cclo = ccs[m]
+                rows, D = streams[m][0].shape[0], streams[m][4]
+                z = torch.empty((rows, 3 * D), dtype=cclo.dtype, device=dev)
+                L.call("k3m_soft_scale", cc.data_ptr(), gate_a[m].data_ptr(), z.data_ptr(), rows, D, L.F32,
+                       ops.dt(z), L.stream())
+                fus[m] = (cc, gate_a[m], z, cclo)
+            with (ops.grouped() if GROUP_GATE else contextlib.nullcontext()):
+                for m in ("v", "t", "pv"):
+                    self.soft[m].fwd(fus[m][2], out=streams[m][3])
+        for m in (() if mode == 2 else ("v", "t", "pv")):
             x0, x1, x2, out, D = streams[m]
             rows = x0.shape[0]
             if mode == 1:
@@ -781,8 +799,9 @@ class K3MEngine(object):
                 L.call("k3m_mean3", x0.data_ptr(), x1.data_ptr(), x2.data_ptr(), out.data_ptr(), out.numel(), L.F32,
                        L.stream())
                 fus[m] = None
-            else:
-                raise NotImplementedError("if_pre_sampling=%s" % mode)
+            else:   # 3, interactive only (:2388-2402): the individual stream does not enter the fusion
+                L.call("k3m_mean2", x1.data_ptr(), x2.data_ptr(), out.data_ptr(), out.numel(), L.F32, L.stream())
+                fus[m] = None
         ctx["fus"] = (fus, streams, mode)
         ctx["seq_tp"], ctx["seq_v"] = seq_tp, seq_v
 
@@ -1097,13 +1116,45 @@ class K3MEngine(object):
                     dc, dpre, dlo, clo = gb[m]
                     self.gate[m].dgrad(dlo, dx=dc, beta=1.0)
                     self.gate[m].wgrad(dlo, clo, bias_done=True)
+        if mode == 2:   # soft gate backward: soft_m input / weight gradients grouped, then the gate as in mode 1
+            sb = {}
+            for m in ("v", "t", "pv"):
+                dout = dslices[m][2]
+                ops.colsum(dout, self.soft[m].gb, accumulate=True)
+                sb[m] = (self._lo(dout), torch.empty_like(fus[m][0]))
+            with (ops.grouped() if GROUP_GATE else contextlib.nullcontext()):
+                for m in ("v", "t", "pv"):
+                    dlo, dz = sb[m]
+                    self.soft[m].dgrad(dlo, dx=dz)
+                    self.soft[m].wgrad(dlo, fus[m][2], bias_done=True)
+            for m in ("v", "t", "pv"):
+                rows, D = streams[m][0].shape[0], streams[m][4]
+                cc, a, z, cclo = fus[m]
+                dz = sb[m][1]
+                # dc overwrites dz element for element; dpre also lands as the gate GEMMs' bf16 operand copy
+                dpre = torch.empty_like(cc)
+                dlo = torch.empty_like(cclo) if cclo.dtype != cc.dtype else None
+                L.call("k3m_soft_scale_bwd", dz.data_ptr(), cc.data_ptr(), a.data_ptr(), dz.data_ptr(), dpre.data_ptr(),
+                       L.ptr(dlo), rows, D, L.F32, L.stream())
+                ops.colsum(dpre, self.gate[m].gb, accumulate=True)
+                gb[m] = (dz, dpre, dlo if dlo is not None else dpre, cclo)
+            with (ops.grouped() if GROUP_GATE else contextlib.nullcontext()):
+                for m in ("v", "t", "pv"):
+                    dc, dpre, dlo, clo = gb[m]
+                    self.gate[m].dgrad(dlo, dx=dc, beta=1.0)
+                    self.gate[m].wgrad(dlo, clo, bias_done=True)
         for m in ("v", "t", "pv"):
             x0 = streams[m][0]
             D = streams[m][4]
             rows = x0.shape[0]
             d1, d2, dout = dslices[m]
+            if mode == 3:   # interactive only: the individual stream gets an exactly zero gradient from the fusion
+                d_ind[m] = torch.zeros_like(x0)
+                L.call("k3m_mean2_bwd", dout.data_ptr(), d1.data_ptr(), d2.data_ptr(), dout.numel(), 0, L.F32,
+                       L.stream())
+                continue
             d0 = torch.empty_like(x0)
-            if mode == 1:
+            if mode in (1, 2):
                 cc = fus[m][0]
                 dc = gb[m][0]
                 L.call("k3m_relu_split3_bwd", dc.data_ptr(), cc.data_ptr(), d0.data_ptr(), d1.data_ptr(), d2.data_ptr(),

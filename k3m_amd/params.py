@@ -21,6 +21,9 @@ Segments, in buffer order: ``decay`` (weight decay 0.01), ``no_decay`` (0.0; nam
 is excluded from the total (train_concap_struc.py:533), ``map_individual_to_bi`` and ``soft_*``
 :2223-2250).  ``pytorch_transformers.AdamW`` skips parameters whose ``.grad`` is None, so the
 frozen segment is never touched by the optimizer — exactly the reference's behaviour.
+The never-grad set follows the fusion mode (``is_frozen(name, cfg)``): 86 tensors for
+``if_pre_sampling`` 0 and 1, 80 for the soft gate (2: ``soft_*`` train), 104 for interactive-only
+(3: the ``score_*`` scorers are unused too).
 """
 import re
 
@@ -171,10 +174,25 @@ _FROZEN_RE = re.compile(r"(\.q_dense[12]\.|^t_pooler\.|^v_pooler\.|^cls\.seq_rel
                         r"^map_individual_to_bi\.|^soft_(v|t|pv)\.)")
 
 
-def is_frozen(name):
+_SOFT_RE = re.compile(r"^soft_(v|t|pv)\.")
+_SCORE_RE = re.compile(r"^score_(self|cross1|cross2)_(v|t|pv)\.")
+
+
+def is_frozen(name, cfg=None):
     """True for the tensors that never get a gradient in the pretraining step (and, the same set
     minus the absent NSP head, in the item-alignment step: its poolers, q_dense*,
-    map_individual_to_bi and soft_* outputs are unused too, vilbert_k3m.py:3183-3376)."""
+    map_individual_to_bi and soft_* outputs are unused too, vilbert_k3m.py:3183-3376).
+
+    The set depends on the fusion mode ``cfg.if_pre_sampling`` (vilbert_k3m.py:2376-2402): the soft
+    gate (2) uses ``soft_*``, so they train; interactive-only (3) uses neither ``soft_*`` nor the
+    ``score_*`` scorers, so both are never-grad.  Pretraining model: 86 tensors in modes 0 and 1
+    (and without ``cfg``), 80 in mode 2, 104 in mode 3.  Mode 0 keeps ``score_*`` trainable with a
+    zero gradient, as it always has."""
+    mode = getattr(cfg, "if_pre_sampling", 1) if cfg is not None else 1
+    if mode == 2 and _SOFT_RE.search(name):
+        return False
+    if mode == 3 and _SCORE_RE.search(name):
+        return True
     return bool(_FROZEN_RE.search(name))
 
 
@@ -182,10 +200,22 @@ def is_no_decay(name):
     return any(nd in name for nd in NO_DECAY)
 
 
-def segment_of(name):
-    if is_frozen(name):
+def segment_of(name, cfg=None):
+    if is_frozen(name, cfg):
         return "frozen"
     return "no_decay" if is_no_decay(name) else "decay"
+
+
+def frozen_names(cfg):
+    """The never-grad names of ``cfg``'s model and fusion mode (a set)."""
+    return {n for n, _ in param_spec(cfg) if is_frozen(n, cfg)}
+
+
+def frozen_of(fp):
+    """The never-grad set of a flat parameter object: ``fp.frozen`` (FlatParams sets it from its
+    config), or the default-mode set by name for an object that carries only a layout."""
+    fz = getattr(fp, "frozen", None)
+    return fz if fz is not None else {n for n, _ in fp.spec if is_frozen(n)}
 
 
 # Groups of parameters that must be adjacent in the flat buffer so that the fused operand is a
@@ -238,11 +268,11 @@ def flat_layout(cfg, align=64):
         pos = (pos + align - 1) // align * align
         start = pos
         for n, _ in spec:
-            if segment_of(n) != seg or n in offsets:
+            if segment_of(n, cfg) != seg or n in offsets:
                 continue
             members = group_of.get(n, [n])
             for m in members:
-                assert segment_of(m) == seg, (m, seg)
+                assert segment_of(m, cfg) == seg, (m, seg)
                 pos = (pos + 3) // 4 * 4
                 offsets[m] = pos
                 pos += numel[m]

@@ -31,7 +31,7 @@ import torch
 
 from . import _lib as L
 from .engine import K3MEngine
-from .params import param_spec, segment_of
+from .params import frozen_of, is_no_decay, param_spec
 
 
 def warmup_linear_lambda(step, warmup, t_total):
@@ -95,15 +95,14 @@ def optimizer_runs(fp, weight_decay=0.01, lr_mult=None, frozen_names=()):
     tensors with equal (weight decay, multiplier).  Lengths are rounded up to 4 floats (16 B): the
     alignment padding between tensors is zero in p, g, m and v and stays zero under the update."""
     lr_mult = lr_mult or {}
-    frozen_names = set(frozen_names)
+    skip = set(frozen_names) | frozen_of(fp)   # --freeze names and the fusion mode's never-grad tensors
     items = []
     for name, shape in fp.spec:
-        seg = segment_of(name)
-        if seg == "frozen" or name in frozen_names:
+        if name in skip:
             continue
         o = fp.offsets[name]
         n = math.prod(shape)
-        items.append((o, o + n, weight_decay if seg == "decay" else 0.0, float(lr_mult.get(name, 1.0))))
+        items.append((o, o + n, 0.0 if is_no_decay(name) else weight_decay, float(lr_mult.get(name, 1.0))))
     items.sort()
     runs = []
     for a, b, wd, mu in items:
@@ -120,14 +119,14 @@ def block_runs(fp, weight_decay=0.01, lr_mult=None, frozen_names=()):
     so that a block's AdamW can run as soon as the backward has finished that block."""
     from .ddp import _block_of
     lr_mult = lr_mult or {}
-    frozen_names = set(frozen_names)
+    skip = set(frozen_names) | frozen_of(fp)
     per = {}
     for name, shape in fp.spec:
-        if segment_of(name) == "frozen" or name in frozen_names:
+        if name in skip:
             continue
         o = fp.offsets[name]
         per.setdefault(_block_of(name), []).append(
-            (o, o + math.prod(shape), weight_decay if segment_of(name) == "decay" else 0.0, float(lr_mult.get(name, 1.0))))
+            (o, o + math.prod(shape), 0.0 if is_no_decay(name) else weight_decay, float(lr_mult.get(name, 1.0))))
     out = {}
     for blk, items in per.items():
         items.sort()
