@@ -219,7 +219,9 @@ int k3m_scale_rows_by_slot(float* x, long long ld, const int32_t* slot, int rows
 int k3m_loss_reduce(const float* loss_rows, const float* row_scale, const int32_t* slot, int rows, float* out,
                     hipStream_t stream);
 /* NSP head forward (seq_relationship(dropout(t+pv+v)) + CE, :1881-1887, :2828-2832); forward only
- * (its loss is excluded from the training total, train_concap_struc.py:533). */
+ * (its loss is excluded from the training total, train_concap_struc.py:533).  The image operand `pv` (the
+ * third pointer; `ppv` is the property-value one) may be NULL: the model without the image modality scores
+ * t + ppv (:1882-1883). */
 int k3m_nsp_loss(const float* pt, const float* ppv, const float* pv, const float* w, const float* b,
                  const int64_t* l0, const int64_t* l1, const int64_t* l2, int batch, int hidden, float* out,
                  hipStream_t stream);
@@ -238,6 +240,19 @@ int k3m_gate_bwd(const void* dout, const float* a, const void* c, const float* y
 /* dx_k (+)= dc[:, kD:(k+1)D] * (c > 0), k = 0..2 (any dx_k may be NULL). */
 int k3m_relu_split3_bwd(const void* dc, const void* c, void* dx0, void* dx1, void* dx2, int rows, int d,
                         int accumulate, int dtype, hipStream_t stream);
+/* Two-candidate gate of the model without the image modality (use_image = False: the individual stream and
+ * one cross stream, pre_sampling_sequence with sequence_c1 = None).  The semantics are those of the four
+ * entry points above with 3 -> 2: c[r, k*D + ch], k in {individual, cross}; a, ys [rows, 2D] fp32; noise
+ * [rows, 2, D] or NULL (counter RNG at off + (r*2 + k)*D + ch); the first maximum wins a tie; idx [rows*D].
+ * Vector accesses: D % 4 == 0, operands on a 4-element boundary (idx on 4 bytes), K3M_EINVAL otherwise.
+ * relu_split2_bwd: either dx_k may be NULL.                                                          */
+int k3m_relu_cat2(const void* x0, const void* x1, void* c, int rows, int d, int dtype, hipStream_t stream);
+int k3m_gate2_fwd(const float* a, const void* c, const float* noise, float* ys, uint8_t* idx, void* out, int rows,
+                  int d, uint64_t seed, uint64_t off, int dtype, hipStream_t stream);
+int k3m_gate2_bwd(const void* dout, const float* a, const void* c, const float* ys, const uint8_t* idx, void* dc,
+                  void* dpre, int rows, int d, int dtype, hipStream_t stream);
+int k3m_relu_split2_bwd(const void* dc, const void* c, void* dx0, void* dx1, int rows, int d, int accumulate,
+                        int dtype, hipStream_t stream);
 /* if_pre_sampling == 0: out = (x0+x1+x2)/3 ; backward: dx_k (+)= dout/3 */
 int k3m_mean3(const void* x0, const void* x1, const void* x2, void* out, long long n, int dtype, hipStream_t stream);
 int k3m_mean3_bwd(const void* dout, void* dx0, void* dx1, void* dx2, long long n, int accumulate, int dtype,

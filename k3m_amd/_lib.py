@@ -72,6 +72,10 @@ SIGNATURES = {
     "k3m_gate_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, u64, u64, i32, vp],
     "k3m_gate_bwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "k3m_relu_split3_bwd": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "k3m_relu_cat2": [vp, vp, vp, i32, i32, i32, vp],
+    "k3m_gate2_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, u64, u64, i32, vp],
+    "k3m_gate2_bwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
+    "k3m_relu_split2_bwd": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "k3m_mean3": [vp, vp, vp, vp, i64, i32, vp],
     "k3m_mean3_bwd": [vp, vp, vp, vp, i64, i32, i32, vp],
     "k3m_soft_scale": [vp, vp, vp, i32, i32, i32, i32, vp],

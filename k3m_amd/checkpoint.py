@@ -62,19 +62,43 @@ def model_state_dict(fp):
     return sd
 
 
+IMAGE_KEY = "v_embeddings.LayerNorm.weight"   # present exactly in the state dicts of the models with the image modality
+
+
+def check_modalities(names, sd):
+    """Refuse a tri-modal state dict for a model without the image modality (use_image false) and the reverse,
+    before anything is copied: the shared tensor names overlap, but the fusion scorers differ in shape (3H vs 2H
+    inputs) and the image-side tensors have no counterpart, so a non-strict load would be a partial one."""
+    model_has, file_has = IMAGE_KEY in set(names), IMAGE_KEY in sd
+    if file_has and not model_has:
+        raise ValueError("the state dict is of a tri-modal model (it holds v_embeddings.*, %d keys) but this model "
+                         "was built without the image modality (use_image=False); nothing was loaded" % len(sd))
+    # an encoder-only file (a BERT checkpoint for --pretrained_model_path) has no fusion scorer and passes
+    if model_has and not file_has and "score_self_t.weight" in sd:
+        raise ValueError("the state dict is of a model without the image modality (use_image=False: no v_embeddings.*, "
+                         "%d keys) but this model is tri-modal; nothing was loaded" % len(sd))
+
+
+def check_shapes(fp, sd):
+    """Every tensor of ``sd`` that the model has must have the model's shape (checked before the first copy)."""
+    for name, _ in fp.spec:
+        if name in sd and tuple(sd[name].shape) != tuple(fp.shapes[name]):
+            raise ValueError("%s: shape %s, expected %s" % (name, tuple(sd[name].shape), fp.shapes[name]))
+
+
 def load_model_state_dict(fp, sd, strict=True):
-    """Copy a (reference or own) state_dict into the flat parameter buffer; strips ``module.``."""
+    """Copy a (reference or own) state_dict into the flat parameter buffer; strips ``module.``.  Modalities and
+    shapes are checked before the first copy: a refused file leaves the parameters as they were."""
     sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
+    check_modalities([n for n, _ in fp.spec], sd)
     missing = [n for n, _ in fp.spec if n not in sd]
     if strict and missing:
         raise KeyError("state_dict lacks %d parameters, e.g. %s" % (len(missing), missing[:4]))
+    check_shapes(fp, sd)
     with torch.no_grad():
         for name, _ in fp.spec:
             if name in sd:
-                t = sd[name]
-                if tuple(t.shape) != tuple(fp.shapes[name]):
-                    raise ValueError("%s: shape %s, expected %s" % (name, tuple(t.shape), fp.shapes[name]))
-                fp.p[name].copy_(t.to(fp.p[name].device, torch.float32))
+                fp.p[name].copy_(sd[name].to(fp.p[name].device, torch.float32))
     fp.shadow_fresh = False
     return missing
 

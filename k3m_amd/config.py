@@ -106,10 +106,12 @@ class BertConfig(object):
 
 
 def pretrain_config(path, with_coattention=True, if_pre_sampling=1, visual_target=0,
-                    dynamic_attention=False, num_negative=255):
+                    dynamic_attention=False, num_negative=255, use_image=True):
     """Load a JSON config and apply the pretraining driver's mutations
-    (train_concap_struc.py:184, :198-211)."""
+    (train_concap_struc.py:184, :198-211).  use_image=False: the model without the image modality
+    (title + property-value knowledge only; the reference's pretrain.py --use_image left off)."""
     cfg = BertConfig.from_json_file(path)
+    cfg.use_image = use_image
     cfg.v_target_size = 1601 if visual_target == 0 else 2048
     cfg.visual_target = visual_target
     cfg.with_coattention = with_coattention

@@ -234,6 +234,126 @@ __global__ void mean2_bwd_kernel(const T* dout, T* dx1, T* dx2, long long n4, in
   }
 }
 
+// ---- two-candidate gate (use_image = False: individual + one cross stream; pre_sampling_sequence with
+// sequence_c1 = None).  c[row, k*D + ch], k in {individual, cross} = torch.cat(feature_list, 2).  Lane i of
+// the flat index owns channels 4*(i % (D/4)) .. +3 of row i / (D/4); d4 = D / 4.
+template <typename T>
+__global__ void relu_cat2_kernel(const T* x0, const T* x1, T* c, long long n4, int d4) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    const long long r = i / d4, b2 = (2 * r * d4 + i % d4) * 4;
+    float u[4], v[4];
+    ld4(x0 + 4 * i, u);
+    ld4(x1 + 4 * i, v);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      u[k] = fmaxf(u[k], 0.f);
+      v[k] = fmaxf(v[k], 0.f);
+    }
+    st4(c + b2, u);
+    st4(c + b2 + 4 * d4, v);
+  }
+}
+
+template <typename T>
+__global__ void gate2_fwd_kernel(const float* a, const T* c, const float* noise, float* ys, uint8_t* idx, T* out,
+                                 long long n4, int d4, uint64_t seed, uint64_t off) {
+  const long long d = 4LL * d4;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    const long long r = i / d4, ch = (i % d4) * 4, b2 = 2 * r * d + ch;
+    float z0[4], z1[4], c0[4], c1[4], g0[4], g1[4], y0[4], y1[4], o[4];
+    ld4(a + b2, z0);
+    ld4(a + b2 + d, z1);
+    ld4(c + b2, c0);
+    ld4(c + b2 + d, c1);
+    if (noise) {   // [rows, 2, D]: the same offsets as the scores
+      ld4(noise + b2, g0);
+      ld4(noise + b2 + d, g1);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        // gumbel(0,1) = -log(Exp(1)) = -log(-log(U))
+        g0[k] = -logf(-logf(k3m_uniform(seed, off + (unsigned long long)(b2 + k))));
+        g1[k] = -logf(-logf(k3m_uniform(seed, off + (unsigned long long)(b2 + d + k))));
+      }
+    }
+    uint32_t pick = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float s0 = z0[k] + g0[k], s1 = z1[k] + g1[k];
+      const float m = fmaxf(s0, s1);
+      const float e0 = expf(s0 - m), e1 = expf(s1 - m);
+      const float inv = 1.f / (e0 + e1);
+      y0[k] = e0 * inv;
+      y1[k] = e1 * inv;
+      const bool one = y1[k] > y0[k];   // the first maximum wins a tie
+      pick |= (one ? 1u : 0u) << (8 * k);
+      o[k] = one ? c1[k] : c0[k];
+    }
+    st4(ys + b2, y0);
+    st4(ys + b2 + d, y1);
+    *reinterpret_cast<uint32_t*>(idx + 4 * i) = pick;
+    st4(out + 4 * i, o);
+  }
+}
+
+template <typename T>
+__global__ void gate2_bwd_kernel(const T* dout, const float* a, const T* c, const float* ys, const uint8_t* idx, T* dc,
+                                 T* dpre, long long n4, int d4) {
+  const long long d = 4LL * d4;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    const long long r = i / d4, ch = (i % d4) * 4, b2 = 2 * r * d + ch;
+    float g[4], a0[4], a1[4], c0[4], c1[4], y0[4], y1[4], dc0[4], dc1[4], p0[4], p1[4];
+    ld4(dout + 4 * i, g);
+    ld4(a + b2, a0);
+    ld4(a + b2 + d, a1);
+    ld4(c + b2, c0);
+    ld4(c + b2 + d, c1);
+    ld4(ys + b2, y0);
+    ld4(ys + b2 + d, y1);
+    const uint32_t pick = *reinterpret_cast<const uint32_t*>(idx + 4 * i);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const bool one = (pick >> (8 * k)) & 0xffu;
+      // softmax' over two candidates: y_q (dy_q - sum_j y_j dy_j) = +-y0 y1 (dy0 - dy1), dy_q = g c_q.  The
+      // factored form has no cancellation against the sum, so a confident pick (y1 ~ 1e-6) keeps its
+      // relative precision and the bf16 rounding of dpre is that of the exact value.
+      const float t = y0[k] * y1[k] * (g[k] * (c0[k] - c1[k]));
+      dc0[k] = one ? 0.f : g[k];
+      dc1[k] = one ? g[k] : 0.f;
+      p0[k] = t * a0[k] * (1.f - a0[k]);
+      p1[k] = -t * a1[k] * (1.f - a1[k]);
+    }
+    st4(dc + b2, dc0);
+    st4(dc + b2 + d, dc1);
+    st4(dpre + b2, p0);
+    st4(dpre + b2 + d, p1);
+  }
+}
+
+template <typename T>
+__global__ void relu_split2_bwd_kernel(const T* dc, const T* c, T* dx0, T* dx1, long long n4, int d4, int acc) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    const long long r = i / d4, b2 = (2 * r * d4 + i % d4) * 4;
+    T* dx[2] = {dx0, dx1};
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      if (!dx[q]) continue;
+      float g[4], cv[4], o[4];
+      ld4(dc + b2 + 4LL * q * d4, g);
+      ld4(c + b2 + 4LL * q * d4, cv);
+      if (acc) {
+        ld4(dx[q] + 4 * i, o);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = 0.f;
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] += cv[k] > 0.f ? g[k] : 0.f;
+      st4(dx[q] + 4 * i, o);
+    }
+  }
+}
+
 // the vector accesses need the operand on a 4-element boundary of its type (NULL passes)
 bool al4(const void* p, int dtype) { return ((uintptr_t)p & (dtype == K3M_BF16 ? 7u : 15u)) == 0; }
 
@@ -290,6 +410,55 @@ extern "C" int k3m_relu_split3_bwd(const void* dc, const void* c, void* dx0, voi
   if (n == 0) return 0;
   DISPATCH_T(dtype, hipLaunchKernelGGL(relu_split3_bwd_kernel<T>, dim3(grid_for(n)), dim3(256), 0, st, (const T*)dc,
                                        (const T*)c, (T*)dx0, (T*)dx1, (T*)dx2, rows, d, accumulate));
+  K3M_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int k3m_relu_cat2(const void* x0, const void* x1, void* c, int rows, int d, int dtype, hipStream_t st) {
+  K3M_ARG(x0 && x1 && c && rows >= 0 && d >= 0 && d % 4 == 0);
+  K3M_ARG(al4(x0, dtype) && al4(x1, dtype) && al4(c, dtype));
+  const long long n4 = (long long)rows * d / 4;
+  if (n4 == 0) return 0;
+  DISPATCH_T(dtype, hipLaunchKernelGGL(relu_cat2_kernel<T>, dim3(grid_for(n4)), dim3(256), 0, st, (const T*)x0,
+                                       (const T*)x1, (T*)c, n4, d / 4));
+  K3M_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int k3m_gate2_fwd(const float* a, const void* c, const float* noise, float* ys, uint8_t* idx, void* out,
+                             int rows, int d, uint64_t seed, uint64_t off, int dtype, hipStream_t st) {
+  K3M_ARG(a && c && ys && idx && out && rows >= 0 && d >= 0 && d % 4 == 0);
+  K3M_ARG(al4(a, K3M_F32) && al4(c, dtype) && al4(noise, K3M_F32) && al4(ys, K3M_F32) && al4(out, dtype) &&
+          ((uintptr_t)idx & 3u) == 0);
+  const long long n4 = (long long)rows * d / 4;
+  if (n4 == 0) return 0;
+  DISPATCH_T(dtype, hipLaunchKernelGGL(gate2_fwd_kernel<T>, dim3(grid_for(n4)), dim3(256), 0, st, a, (const T*)c,
+                                       noise, ys, idx, (T*)out, n4, d / 4, seed, off));
+  K3M_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int k3m_gate2_bwd(const void* dout, const float* a, const void* c, const float* ys, const uint8_t* idx,
+                             void* dc, void* dpre, int rows, int d, int dtype, hipStream_t st) {
+  K3M_ARG(dout && a && c && ys && idx && dc && dpre && rows >= 0 && d >= 0 && d % 4 == 0);
+  K3M_ARG(al4(dout, dtype) && al4(a, K3M_F32) && al4(c, dtype) && al4(ys, K3M_F32) && al4(dc, dtype) &&
+          al4(dpre, dtype) && ((uintptr_t)idx & 3u) == 0);
+  const long long n4 = (long long)rows * d / 4;
+  if (n4 == 0) return 0;
+  DISPATCH_T(dtype, hipLaunchKernelGGL(gate2_bwd_kernel<T>, dim3(grid_for(n4)), dim3(256), 0, st, (const T*)dout, a,
+                                       (const T*)c, ys, idx, (T*)dc, (T*)dpre, n4, d / 4));
+  K3M_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int k3m_relu_split2_bwd(const void* dc, const void* c, void* dx0, void* dx1, int rows, int d, int accumulate,
+                                   int dtype, hipStream_t st) {
+  K3M_ARG(dc && c && rows >= 0 && d >= 0 && d % 4 == 0);
+  K3M_ARG(al4(dc, dtype) && al4(c, dtype) && al4(dx0, dtype) && al4(dx1, dtype));
+  const long long n4 = (long long)rows * d / 4;
+  if (n4 == 0) return 0;
+  DISPATCH_T(dtype, hipLaunchKernelGGL(relu_split2_bwd_kernel<T>, dim3(grid_for(n4)), dim3(256), 0, st, (const T*)dc,
+                                       (const T*)c, (T*)dx0, (T*)dx1, n4, d / 4, accumulate));
   K3M_CHECK_LAUNCH();
   return 0;
 }

@@ -149,7 +149,8 @@ __global__ __launch_bounds__(256) void nsp_kernel(const float* pt, const float* 
   for (int i = 0; i < batch; ++i) {
     float z0 = 0.f, z1 = 0.f;
     for (int c = threadIdx.x; c < hidden; c += 256) {
-      const float x = pt[(long long)i * hidden + c] + ppv[(long long)i * hidden + c] + pv[(long long)i * hidden + c];
+      float x = pt[(long long)i * hidden + c] + ppv[(long long)i * hidden + c];
+      if (pv) x += pv[(long long)i * hidden + c];   // NULL: no image modality (:1882-1883)
       z0 += x * w[c];
       z1 += x * w[hidden + c];
     }
@@ -217,7 +218,7 @@ extern "C" int k3m_loss_reduce(const float* loss_rows, const float* row_scale, c
 extern "C" int k3m_nsp_loss(const float* pt, const float* ppv, const float* pv, const float* w, const float* b,
                             const int64_t* l0, const int64_t* l1, const int64_t* l2, int batch, int hidden, float* out,
                             hipStream_t st) {
-  K3M_ARG(pt && ppv && pv && w && b && l0 && l1 && l2 && out && batch > 0);
+  K3M_ARG(pt && ppv && w && b && l0 && l1 && l2 && out && batch > 0);
   hipLaunchKernelGGL(nsp_kernel, dim3(1), dim3(256), 0, st, pt, ppv, pv, w, b, l0, l1, l2, batch, hidden, out);
   K3M_CHECK_LAUNCH();
   return 0;

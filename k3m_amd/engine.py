@@ -470,13 +470,23 @@ def label_counts(batch):
     A loader that builds the batch on the host stores them as batch["_label_counts"] so the forward
     needs no device->host sync; this helper computes them from a batch (one sync)."""
     n_m = int((batch["lm_label_ids"] >= 0).sum()) + int((batch["lm_label_ids_pv"] >= 0).sum())
-    n_v = int((batch["image_label"] >= 1).sum())
+    n_v = int((batch["image_label"] >= 1).sum()) if "image_label" in batch else 0   # absent: no image modality
     return (n_m, n_v)
 
 
 def _ext_mask(m):
     # (1 - mask) * -10000 additive key mask (vilbert_k3m.py:2547-2580); input marshalling
     return ((1.0 - m.to(torch.float32)) * -10000.0).contiguous()
+
+
+def validate_config(cfg):
+    """Configurations the engine refuses, checked before any device work.  Without the image modality
+    (use_image false) the reference defines only the hard gate: its fusion modes 0, 2 and 3 add the absent
+    image-side stream (``None``) and raise TypeError (vilbert_k3m.py:2388-2402)."""
+    if not getattr(cfg, "use_image", True) and getattr(cfg, "if_pre_sampling", 1) != 1:
+        raise ValueError("use_image=False with if_pre_sampling=%s: the reference defines only the hard gate "
+                         "(if_pre_sampling=1) for the model without the image modality"
+                         % getattr(cfg, "if_pre_sampling", 1))
 
 
 class K3MEngine(object):
@@ -487,6 +497,7 @@ class K3MEngine(object):
         co-attention layers, >95% of the FLOPs — keeps activations and activation gradients in bf16
         and multiplies the bf16 weight shadow on the bf16 MFMA; embeddings, fusion, heads, losses,
         parameter gradients and AdamW stay fp32)."""
+        validate_config(cfg)
         self.cfg = cfg
         self.device = torch.device(device if device is not None else "cuda")
         L.load()
@@ -509,8 +520,10 @@ class K3MEngine(object):
         assert getattr(c, "fixed_t_layer", 0) == 0 and getattr(c, "fixed_v_layer", 0) == 0
         assert not getattr(c, "in_batch_pairs", False) and not getattr(c, "fast_mode", False)
         assert not getattr(c, "dynamic_attention", False) and getattr(c, "model", "bert") in ("bert", "roberta")
-        assert getattr(c, "use_image", True) and c.with_coattention
+        assert c.with_coattention
         assert getattr(c, "visual_target", 0) == 0
+        # False: the model without the image modality — the forward / backward pair of k3m_amd/engine_text.py
+        self.use_image = bool(getattr(c, "use_image", True))
         self.H, self.Hv, self.Hb = c.hidden_size, c.v_hidden_size, c.bi_hidden_size
         self.p_h = c.hidden_dropout_prob
         self.p_a = c.attention_probs_dropout_prob
@@ -518,35 +531,41 @@ class K3MEngine(object):
         self.p_va = c.v_attention_probs_dropout_prob
         self.text = [BertLayerOp(fp, "encoder.layer.%d" % i, c.num_attention_heads, self.p_a, self.p_h)
                      for i in range(c.num_hidden_layers)]
-        self.image = [BertLayerOp(fp, "encoder.v_layer.%d" % i, c.v_num_attention_heads, self.p_va, self.p_vh)
-                      for i in range(c.v_num_hidden_layers)]
         nco = len(c.v_biattention_id)
         nb = c.bi_num_attention_heads
-        self.co_tv = [ConnectionOp(fp, "encoder.c_layer.%d" % i, nb, self.p_va, self.p_a, self.p_vh, self.p_h,
-                                   self.p_vh, self.p_h) for i in range(nco)]
-        self.co_pv = [ConnectionOp(fp, "encoder.c_layer_pv_v.%d" % i, nb, self.p_va, self.p_a, self.p_vh, self.p_h,
-                                   self.p_vh, self.p_h) for i in range(nco)]
         self.co_tt = [ConnectionOp(fp, "encoder.c_layer_pv_t.%d" % i, nb, self.p_va, self.p_a, self.p_vh, self.p_h,
                                    self.p_h, self.p_h) for i in range(nco)]
         self.emb_ln = LN(fp, "embeddings.LayerNorm")
-        self.vemb_img = Lin(fp, "v_embeddings.image_embeddings")
-        self.vemb_loc = Lin(fp, "v_embeddings.image_location_embeddings")
-        self.vemb_ln = LN(fp, "v_embeddings.LayerNorm")
-        self.gate = {m: Lin(fp, ["score_self_%s" % m, "score_cross1_%s" % m, "score_cross2_%s" % m])
-                     for m in ("v", "t", "pv")}
-        self.soft = {m: Lin(fp, "soft_%s" % m) for m in ("v", "t", "pv")}   # if_pre_sampling == 2 only
-        self.map_b2i = Lin(fp, "map_bi_to_individual")
+        if self.use_image:
+            self.image = [BertLayerOp(fp, "encoder.v_layer.%d" % i, c.v_num_attention_heads, self.p_va, self.p_vh)
+                          for i in range(c.v_num_hidden_layers)]
+            self.co_tv = [ConnectionOp(fp, "encoder.c_layer.%d" % i, nb, self.p_va, self.p_a, self.p_vh, self.p_h,
+                                       self.p_vh, self.p_h) for i in range(nco)]
+            self.co_pv = [ConnectionOp(fp, "encoder.c_layer_pv_v.%d" % i, nb, self.p_va, self.p_a, self.p_vh,
+                                       self.p_h, self.p_vh, self.p_h) for i in range(nco)]
+            self.vemb_img = Lin(fp, "v_embeddings.image_embeddings")
+            self.vemb_loc = Lin(fp, "v_embeddings.image_location_embeddings")
+            self.vemb_ln = LN(fp, "v_embeddings.LayerNorm")
+            self.gate = {m: Lin(fp, ["score_self_%s" % m, "score_cross1_%s" % m, "score_cross2_%s" % m])
+                         for m in ("v", "t", "pv")}
+            self.soft = {m: Lin(fp, "soft_%s" % m) for m in ("v", "t", "pv")}   # if_pre_sampling == 2 only
+            self.map_b2i = Lin(fp, "map_bi_to_individual")
+        else:   # two-candidate gate: [score_self_m | score_cross2_m] is one [2H, 2H] weight view
+            self.gate = {m: Lin(fp, ["score_self_%s" % m, "score_cross2_%s" % m]) for m in ("t", "pv")}
         # "pretrain": the pretraining heads + LPM; "item_alignment": the encoder up to c_final only
         # (K3MForItemAlignment.item_embedding, vilbert_k3m.py:3329-3377; its pair head is k3m_amd.finetune)
         self.task = getattr(c, "task", "pretrain")
         if self.task == "pretrain":
             self.mlm_t = Lin(fp, "cls.predictions.transform.dense")
             self.mlm_ln = LN(fp, "cls.predictions.transform.LayerNorm")
-            self.img_t = Lin(fp, "cls.imagePredictions.transform.dense")
-            self.img_ln = LN(fp, "cls.imagePredictions.transform.LayerNorm")
-            self.img_dec = Lin(fp, "cls.imagePredictions.decoder")
+            if self.use_image:
+                self.img_t = Lin(fp, "cls.imagePredictions.transform.dense")
+                self.img_ln = LN(fp, "cls.imagePredictions.transform.LayerNorm")
+                self.img_dec = Lin(fp, "cls.imagePredictions.decoder")
         self.sw1, self.sw3 = Lin(fp, "struc_w1"), Lin(fp, "struc_w3")
         self.schedule = self._schedule()
+        if not self.use_image:
+            self.schedule = [s for s in self.schedule if s[0] != "v"]
 
     def _lo(self, x):
         """bf16 operand copy of an fp32 activation for the large fp32-region GEMMs (fusion gates, tied
@@ -608,7 +627,14 @@ class K3MEngine(object):
         ent_neg/val_neg optional [B,NPV,2].
         groups: the batch is that many independent model calls stacked along dim 0 (the item
         alignment pair: item 1 rows then item 2 rows); only the structure aggregator's
-        zero-triple fallback crosses items, and it is kept inside each group."""
+        zero-triple fallback crosses items, and it is kept inside each group.
+
+        Without the image modality (cfg.use_image false) the step is k3m_amd/engine_text.py's: noise is
+        {t: [B,T,2,H], pv: [B,P,2,H]} and the image fields of the batch may be absent (they are not read)."""
+        if not self.use_image:
+            from . import engine_text
+            return engine_text.forward(self, batch, train=train, noise=noise, ent_neg=ent_neg, val_neg=val_neg,
+                                       seed=seed, groups=groups)
         c = self.cfg
         fp = self.fp
         if debug.ON:
@@ -984,6 +1010,10 @@ class K3MEngine(object):
             self._backward(ctx, w_mlm, w_img, w_lpm, hook, w_mlm_pv)
 
     def _backward(self, ctx, w_mlm=1.0, w_img=1.0, w_lpm=1.0, grad_ready=None, w_mlm_pv=None):
+        if not self.use_image:   # the image loss is a constant: w_img weights nothing
+            from . import engine_text
+            return engine_text.backward(self, ctx, w_mlm=w_mlm, w_lpm=w_lpm, grad_ready=grad_ready,
+                                        w_mlm_pv=w_mlm_pv)
         c = self.cfg
         fp = self.fp
         dev = self.device

@@ -1,0 +1,360 @@
+"""The K3M step without the image modality (``cfg.use_image`` false): title + property-value knowledge only.
+
+Reference: the ``use_image=False`` branches of BertForMultiModalPreTraining_tri_stru / K3MForItemAlignment
+(vilbert_k3m/vilbert_k3m.py) — BertEncoder keeps ``layer`` and ``c_layer_pv_t`` (:1724-1743,
+calculate_for_two_text :1510), the fusion gate chooses between the individual stream and the one cross stream
+(pre_sampling_sequence :2331-2374 with ``sequence_c1 = None``), ``c_initial = (pooled_t + pooled_pv) / 2`` (:2725),
+the NSP score uses ``pooled_t + pooled_pv`` (:1882-1883) and the image loss is a constant zero (:2815).  Only the
+hard gate (if_pre_sampling 1) is defined upstream for this model; K3MEngine refuses the others.
+
+A separate forward / backward pair over the op classes of k3m_amd/engine.py, so the tri-modal pair is untouched.
+Layout: ONE text buffer [B*T + B*P, 768] = [title | PV] — no duplicated streams (each stream has a single
+partner) and no image work.  The title and PV rows are adjacent in every fusion buffer, so relu-cat, gate and
+relu-split each run as one launch over both modalities; only the two scorer GEMMs (different weights) are per
+modality, grouped into one launch under GROUP_GATE.
+"""
+import contextlib
+
+import torch
+
+from . import debug
+from . import _lib as L
+from . import engine as E
+from . import ops
+
+
+def _views(eng, train):
+    return (lambda op: op) if train else E._eval_view
+
+
+def forward(eng, batch, train=True, noise=None, ent_neg=None, val_neg=None, seed=None, groups=1):
+    """K3MEngine.forward for use_image=False.  noise: optional {t: [B,T,2,H], pv: [B,P,2,H]}.  The image
+    fields of ``batch`` (image_feat, image_loc, image_mask, image_label, image_target) are not read."""
+    c, fp, dev = eng.cfg, eng.fp, eng.device
+    if debug.ON:
+        debug.check_batch(batch, c, ent_neg, val_neg)
+    fp.refresh_shadow()
+    H, ED = eng.H, eng.enc_dtype
+    ids, tt, mt = batch["input_ids"], batch["segment_ids"], batch["input_mask"]
+    pids, ptt, mp = batch["input_ids_pv"], batch["segment_ids_pv"], batch["input_mask_pv"]
+    B, T = ids.shape
+    P = pids.shape[1]
+    BT, BP = B * T, B * P
+    Nt = BT + BP
+    rng = E.Rng(eng.base_seed * 1000003 + (seed if seed is not None else eng.step_count))
+    ph = eng.p_h if train else 0.0
+    ctx = {"B": B, "T": T, "P": P, "train": train, "seed": rng.seed}
+    mask_t, mask_p = E._ext_mask(mt), E._ext_mask(mp)
+    f32 = dict(dtype=torch.float32, device=dev)
+
+    # ---- embeddings: the individual copies and the encoder input, one launch per stream
+    XT = torch.empty((Nt, H), **f32)
+    ind = torch.empty((Nt, H), **f32)
+    xh = torch.empty((Nt, H), **f32)
+    rs = torch.empty((Nt,), **f32)
+    emb = (fp.p["embeddings.word_embeddings.weight"], fp.p["embeddings.position_embeddings.weight"],
+           fp.p["embeddings.token_type_embeddings.weight"], eng.emb_ln.g, eng.emb_ln.b)
+    off_t = rng.take(BT * H) if ph > 0 else 0
+    ops.embed_fwd(ids, tt, *emb, ind[0:BT], XT[0:BT], None, xh[0:BT], rs[0:BT], ph, rng.seed, off_t)
+    off_p = rng.take(BP * H) if ph > 0 else 0
+    ops.embed_fwd(pids, ptt, *emb, ind[BT:], XT[BT:], None, xh[BT:], rs[BT:], ph, rng.seed, off_p)
+    ctx["emb"] = (xh, rs, off_t, off_p)
+    if ED != torch.float32:
+        XT = ops.convert(XT, torch.empty((Nt, H), dtype=ED, device=dev))
+
+    # ---- encoder: text layers over (B, T) and (B, P); co_tt[i] alone at each ('c', i)
+    view = _views(eng, train)
+    tsegs = [(0, B, T, mask_t), (BT, B, P, mask_p)]
+    enc = []
+    for kind, i in eng.schedule:
+        if kind == "t":
+            XT, sv = view(eng.text[i]).fwd(XT, tsegs, rng)
+            enc.append((kind, i, sv))
+        else:   # stream 1 = PV, stream 2 = title (BertConnectionLayer_two_text)
+            op = view(eng.co_tt[i])
+            XT2 = torch.empty_like(XT)
+            args = (XT[BT:], XT[0:BT], B, P, T, mask_p, mask_t, rng, XT2[BT:], XT2[0:BT])
+            if E.GROUPED:
+                res = []
+                E._lockstep([op.fwd_steps(*args, res=res)])
+                sv = res[0]
+            else:
+                sv = op.fwd(*args)
+            enc.append((kind, i, (sv, op)))
+            XT = XT2
+    ctx["enc"] = enc
+    if ED != torch.float32:   # encoder -> fp32 fusion / heads
+        XT = ops.convert(XT, torch.empty((Nt, H), **f32))
+
+    # ---- two-candidate hard gate over [individual | cross]
+    cc = torch.empty((Nt, 2 * H), **f32)
+    L.call("k3m_relu_cat2", ind.data_ptr(), XT.data_ptr(), cc.data_ptr(), Nt, H, L.F32, L.stream())
+    cclo = eng._lo(cc)
+    a = torch.empty((Nt, 2 * H), **f32)
+    with (ops.grouped() if E.GROUP_GATE else contextlib.nullcontext()):
+        eng.gate["t"].fwd(cclo[0:BT], out=a[0:BT], epi=L.EPI_BIAS_SIGMOID)
+        eng.gate["pv"].fwd(cclo[BT:], out=a[BT:], epi=L.EPI_BIAS_SIGMOID)
+    ys = torch.empty_like(a)
+    idx = torch.empty((Nt * H,), dtype=torch.uint8, device=dev)
+    seq_tp = torch.empty((Nt, H), **f32)
+    nz, off_g = None, 0
+    if noise is not None:
+        nz = torch.cat([noise["t"].reshape(BT, 2 * H), noise["pv"].reshape(BP, 2 * H)]).to(**f32).contiguous()
+    else:
+        off_g = rng.take(Nt * 2 * H)
+    L.call("k3m_gate2_fwd", a.data_ptr(), cc.data_ptr(), L.ptr(nz), ys.data_ptr(), idx.data_ptr(), seq_tp.data_ptr(),
+           Nt, H, rng.seed, off_g, L.F32, L.stream())
+    ctx["fus"] = (cc, a, ys, idx)
+    ctx["seq_tp"] = seq_tp
+
+    # ---- pooled outputs and c_initial (:2408-2409, :2725)
+    pooled_t = torch.empty((B, H), **f32)
+    pooled_pv = torch.empty((B, H), **f32)
+    L.call("k3m_seq_mean", seq_tp.data_ptr(), B, T, 1, H, 1.0, pooled_t.data_ptr(), 0, L.F32, L.stream())
+    L.call("k3m_seq_mean", seq_tp[BT:].data_ptr(), B, P, 1, H, 1.0, pooled_pv.data_ptr(), 0, L.F32, L.stream())
+    c_init = torch.empty((B, H), **f32)
+    L.call("k3m_mean2", pooled_t.data_ptr(), pooled_pv.data_ptr(), c_init.data_ptr(), c_init.numel(), L.F32, L.stream())
+
+    # ---- structure aggregator + LPM (:2413-2505), as the tri-modal step
+    index_p, index_v = batch["index_p"].contiguous(), batch["index_v"].contiguous()
+    NPV = index_p.shape[1]
+    X = torch.empty((B * NPV, 3 * H), **f32)
+    nvalid = torch.empty((B,), dtype=torch.int32, device=dev)
+    src = torch.empty((B,), dtype=torch.int32, device=dev)
+    assert B % groups == 0
+    Bg = B // groups
+    for gi in range(groups):   # src (zero-triple fallback) is group-relative
+        r0 = gi * Bg
+        L.call("k3m_sa_gather", seq_tp[BT + r0 * P:].data_ptr(), index_p[r0:].data_ptr(), index_v[r0:].data_ptr(),
+               c_init[r0:].data_ptr(), X[r0 * NPV:].data_ptr(), nvalid[r0:].data_ptr(), src[r0:].data_ptr(), Bg, P,
+               NPV, H, L.F32, L.stream())
+    Tm = eng.sw1.fwd(X)
+    att = torch.empty((B, NPV), **f32)
+    agg = torch.empty((B, H), **f32)
+    for gi in range(groups):
+        r0 = gi * Bg
+        L.call("k3m_sa_attn_fwd", Tm[r0 * NPV:].data_ptr(), nvalid[r0:].data_ptr(), src[r0:].data_ptr(),
+               fp.p["struc_w2.weight"].data_ptr(), fp.p["struc_w2.bias"].data_ptr(), c_init[r0:].data_ptr(),
+               att[r0:].data_ptr(), agg[r0:].data_ptr(), Bg, NPV, H, L.stream())
+    c_final = c_init.clone()
+    eng.sw3.fwd(agg, out=c_final, beta=1.0)
+    ctx["groups"] = groups
+    ctx["batch"] = batch
+    if eng.task != "pretrain":
+        ctx["struct"] = (X, nvalid, src, Tm, att, agg, c_init, c_final, None, None, None, index_p, index_v, NPV, None)
+        return {"c_initial": c_init, "c_final": c_final, "pooled_t": pooled_t, "pooled_pv": pooled_pv,
+                "pooled_v": None}, ctx
+    assert groups == 1
+    nneg = int(getattr(c, "num_negative_pv", 4))
+    if ent_neg is None:
+        ke, kv = nneg // 2, nneg - nneg // 2   # vilbert_k3m.py:2476, :2488
+        ent_neg = torch.empty((B, NPV, ke), dtype=torch.int64, device=dev)
+        val_neg = torch.empty((B, NPV, kv), dtype=torch.int64, device=dev)
+        L.call("k3m_lpm_sample", nvalid.data_ptr(), B, NPV, ke, kv, rng.seed, rng.take(B * NPV * (ke + kv)),
+               L.ptr(ent_neg), L.ptr(val_neg), L.stream())
+    else:
+        ent_neg = ent_neg.to(device=dev, dtype=torch.int64).contiguous()
+        val_neg = val_neg.to(device=dev, dtype=torch.int64).contiguous()
+        ke, kv = ent_neg.shape[2], val_neg.shape[2]
+    lpm = torch.empty((1,), **f32)
+    lws = torch.empty((B * NPV * (2 * (ke + kv) + 1) + 2,), **f32)
+    margin = float(getattr(c, "margin", 1.0))
+    L.call("k3m_lpm_fwd", c_final.data_ptr(), X.data_ptr(), nvalid.data_ptr(), L.ptr(ent_neg), L.ptr(val_neg), B, NPV,
+           H, ke, kv, margin, lpm.data_ptr(), lws.data_ptr(), L.stream())
+    ctx["struct"] = (X, nvalid, src, Tm, att, agg, c_init, c_final, ent_neg, val_neg, lws, index_p, index_v, NPV,
+                     margin)
+
+    # ---- MLM head on the labelled rows; slot 2 of `losses` (the image loss) stays an exact zero (:2815)
+    losses = torch.zeros((4,), **f32)
+    idx_m = torch.zeros((Nt,), dtype=torch.int32, device=dev)
+    lab_m = torch.zeros((Nt,), dtype=torch.int64, device=dev)
+    sc_m = torch.zeros((Nt,), **f32)
+    sl_m = torch.zeros((Nt,), dtype=torch.int32, device=dev)
+    cnt = torch.zeros((2,), dtype=torch.int32, device=dev)
+    L.call("k3m_compact_labels_ex", batch["lm_label_ids"].contiguous().data_ptr(), BT, 0, T, T, 0, 0,
+           idx_m.data_ptr(), lab_m.data_ptr(), None, sc_m.data_ptr(), sl_m.data_ptr(), cnt.data_ptr(), L.stream())
+    L.call("k3m_compact_labels_ex", batch["lm_label_ids_pv"].contiguous().data_ptr(), BP, 0, P, P, BT, 1,
+           idx_m.data_ptr(), lab_m.data_ptr(), None, sc_m.data_ptr(), sl_m.data_ptr(), cnt.data_ptr(), L.stream())
+    hint = batch.get("_label_counts")
+    if hint is not None:   # the region count of a loader's hint belongs to the unused image fields
+        n_m = int(hint[0])
+        eng._verify_hint((n_m, 0), cnt)
+    else:
+        n_m = int(cnt[0])   # host sync (labelled-row count)
+    V = c.vocab_size
+    hm = torch.empty((n_m, H), **f32)
+    ops.gather_rows(seq_tp, idx_m, n_m, hm)
+    pre_m = torch.empty_like(hm)
+    hm1 = eng.mlm_t.fwd(hm, epi=L.EPI_BIAS_GELU, aux=pre_m)
+    hl = torch.empty_like(hm)
+    xh_m = torch.empty_like(hm)
+    rs_m = torch.empty((n_m,), **f32)
+    if n_m:
+        ops.ln_fwd(hm1, None, eng.mlm_ln.g, eng.mlm_ln.b, hl, xh_m, rs_m)
+    bf = eng.dtype == "bf16"
+    Ew = fp.p16("embeddings.word_embeddings.weight") if bf else fp.p["embeddings.word_embeddings.weight"]
+    logits = ops.linear(eng._lo(hl), Ew, fp.p["cls.predictions.bias"], out_dtype=torch.float32)
+    captured = {"mlm_logits": logits.clone()} if eng.capture_logits else {}   # the CE kernel overwrites the logits
+    lr_m = torch.empty((n_m,), **f32)
+    L.call("k3m_ce_fwd_bwd", logits.data_ptr(), V, lab_m.data_ptr(), sc_m.data_ptr(), n_m, V, lr_m.data_ptr(),
+           L.stream())
+    if n_m:
+        L.call("k3m_loss_reduce", lr_m.data_ptr(), sc_m.data_ptr(), sl_m.data_ptr(), n_m, losses.data_ptr(), L.stream())
+    ctx["mlm"] = (idx_m, n_m, hm, pre_m, hl, xh_m, rs_m, logits)
+    ctx["mlm_slot"] = sl_m
+
+    nsp = torch.empty((1,), **f32)
+    L.call("k3m_nsp_loss", pooled_t.data_ptr(), pooled_pv.data_ptr(), None,
+           fp.p["cls.seq_relationship.weight"].data_ptr(), fp.p["cls.seq_relationship.bias"].data_ptr(),
+           batch["is_next"].contiguous().data_ptr(), batch["is_next_pv_v"].contiguous().data_ptr(),
+           batch["is_next_pv_t"].contiguous().data_ptr(), B, H, nsp.data_ptr(), L.stream())
+    out = {
+        "masked_lm_loss": losses[0:1], "masked_lm_loss_pv": losses[1:2], "masked_img_loss": losses[2:3],
+        "loss_lpm": lpm, "next_sentence_loss": nsp, "c_initial": c_init, "c_final": c_final,
+        "pooled_t": pooled_t, "pooled_pv": pooled_pv, "pooled_v": None,
+    }
+    out["loss"] = losses[0:1] + losses[1:2] + losses[2:3] + lpm
+    out.update(captured)
+    return out, ctx
+
+
+def backward(eng, ctx, w_mlm=1.0, w_lpm=1.0, grad_ready=None, w_mlm_pv=None):
+    """K3MEngine._backward for use_image=False: no image gradient buffers or launches, and nothing accumulates
+    into the never-grad score_cross1_*."""
+    fp, dev = eng.fp, eng.device
+    H = eng.H
+    B, T, P = ctx["B"], ctx["T"], ctx["P"]
+    BT, BP = B * T, B * P
+    Nt = BT + BP
+    batch = ctx["batch"]
+    seq_tp = ctx["seq_tp"]
+    dseq_tp = torch.zeros_like(seq_tp)
+    f32 = dict(dtype=torch.float32, device=dev)
+
+    # ---- MLM head (dlogits already in place from the forward CE kernel)
+    idx_m, n_m, hm, pre_m, hl, xh_m, rs_m, dlog = ctx["mlm"] if "mlm" in ctx else (None, 0) + (None,) * 6
+    if n_m and w_mlm_pv is not None and w_mlm_pv != w_mlm:
+        L.call("k3m_scale_rows_by_slot", dlog.data_ptr(), dlog.shape[1], ctx["mlm_slot"].data_ptr(), n_m,
+               dlog.shape[1], w_mlm, w_mlm_pv, L.stream())
+        w_mlm = 1.0
+    if n_m:
+        bf = eng.dtype == "bf16"
+        Ew = fp.p16("embeddings.word_embeddings.weight") if bf else fp.p["embeddings.word_embeddings.weight"]
+        dlo = eng._lo(dlog)
+        dhl = ops.linear_dgrad(dlo, Ew, dx=torch.empty(hl.shape, **f32), alpha=w_mlm)
+        ops.linear_wgrad(dlo, eng._lo(hl), fp.g["embeddings.word_embeddings.weight"], None, alpha=w_mlm)
+        ops.colsum(dlog, fp.g["cls.predictions.bias"], accumulate=True, alpha=w_mlm)
+        dh1 = torch.empty_like(hl)
+        ops.ln_bwd(dhl, xh_m, rs_m, eng.mlm_ln.g, dh1, dh1, eng.mlm_ln.gg, eng.mlm_ln.gb)
+        du = torch.empty_like(hl)
+        ops.dgelu(dh1, pre_m, du)
+        eng.mlm_t.wgrad(du, hm)
+        dhm = eng.mlm_t.dgrad(du)
+        ops.scatter_add_rows(dhm, idx_m, n_m, dseq_tp)
+
+    # ---- structure aggregator + LPM
+    (X, nvalid, src, Tm, att, agg, c_init, c_final, ent_neg, val_neg, lws, index_p, index_v, NPV,
+     margin) = ctx["struct"]
+    dcf = torch.zeros_like(c_final)
+    dX = torch.zeros_like(X)
+    det = ops.DETERMINISTIC
+    if lws is not None:
+        if det:
+            L.call("k3m_lpm_bwd_det", c_final.data_ptr(), X.data_ptr(), nvalid.data_ptr(), L.ptr(ent_neg),
+                   L.ptr(val_neg), B, NPV, H, ent_neg.shape[2], val_neg.shape[2], lws.data_ptr(), dcf.data_ptr(),
+                   dX.data_ptr(), L.stream())
+        else:
+            L.call("k3m_lpm_bwd", c_final.data_ptr(), X.data_ptr(), nvalid.data_ptr(), L.ptr(ent_neg),
+                   L.ptr(val_neg), B, NPV, H, ent_neg.shape[2], val_neg.shape[2], margin, lws.data_ptr(),
+                   dcf.data_ptr(), dX.data_ptr(), L.stream())
+        if w_lpm != 1.0:
+            ops.add_(dcf, dcf.clone(), w_lpm - 1.0)
+            ops.add_(dX, dX.clone(), w_lpm - 1.0)
+    if "d_c_final" in ctx:
+        ops.add_(dcf, ctx["d_c_final"].contiguous())
+    dagg = eng.sw3.dgrad(dcf)
+    eng.sw3.wgrad(dcf, agg)
+    dci = dcf.clone()                                   # c_final = c_init + ...
+    if "d_c_initial" in ctx:
+        ops.add_(dci, ctx["d_c_initial"].contiguous())
+    dT = torch.zeros_like(Tm)
+    groups = ctx.get("groups", 1)
+    Bg = B // groups
+    sa_ws = torch.empty((Bg * (H + 1),), **f32) if det else None
+    for gi in range(groups):
+        r0 = gi * Bg
+        if det:
+            L.call("k3m_sa_attn_bwd_det", dagg[r0:].data_ptr(), Tm[r0 * NPV:].data_ptr(), att[r0:].data_ptr(),
+                   nvalid[r0:].data_ptr(), src[r0:].data_ptr(), fp.p["struc_w2.weight"].data_ptr(),
+                   dT[r0 * NPV:].data_ptr(), fp.g["struc_w2.weight"].data_ptr(), fp.g["struc_w2.bias"].data_ptr(),
+                   dci[r0:].data_ptr(), sa_ws.data_ptr(), Bg, NPV, H, L.stream())
+        else:
+            L.call("k3m_sa_attn_bwd", dagg[r0:].data_ptr(), Tm[r0 * NPV:].data_ptr(), att[r0:].data_ptr(),
+                   nvalid[r0:].data_ptr(), src[r0:].data_ptr(), fp.p["struc_w2.weight"].data_ptr(),
+                   dT[r0 * NPV:].data_ptr(), fp.g["struc_w2.weight"].data_ptr(), fp.g["struc_w2.bias"].data_ptr(),
+                   dci[r0:].data_ptr(), Bg, NPV, H, L.stream())
+    eng.sw1.wgrad(dT, X)
+    eng.sw1.dgrad(dT, dx=dX, beta=1.0)
+    L.call("k3m_sa_gather_bwd_det" if det else "k3m_sa_gather_bwd", dX.data_ptr(), index_p.data_ptr(),
+           index_v.data_ptr(), nvalid.data_ptr(), dseq_tp[BT:].data_ptr(), dci.data_ptr(), B, P, NPV, H, L.F32,
+           L.stream())
+
+    # ---- pooled outputs: c_initial = (pooled_t + pooled_pv) / 2
+    dpt = torch.empty((B, H), **f32)
+    dppv = torch.empty((B, H), **f32)
+    L.call("k3m_mean2_bwd", dci.data_ptr(), dpt.data_ptr(), dppv.data_ptr(), dci.numel(), 0, L.F32, L.stream())
+    L.call("k3m_seq_mean_bwd", dpt.data_ptr(), B, T, 1, H, 1.0, dseq_tp.data_ptr(), L.F32, L.stream())
+    L.call("k3m_seq_mean_bwd", dppv.data_ptr(), B, P, 1, H, 1.0, dseq_tp[BT:].data_ptr(), L.F32, L.stream())
+
+    # ---- gate: elementwise part over both modalities, the two modalities' GEMMs grouped, relu-split
+    cc, a, ys, idx = ctx["fus"]
+    dc = torch.empty_like(cc)
+    dpre = torch.empty_like(cc)
+    L.call("k3m_gate2_bwd", dseq_tp.data_ptr(), a.data_ptr(), cc.data_ptr(), ys.data_ptr(), idx.data_ptr(),
+           dc.data_ptr(), dpre.data_ptr(), Nt, H, L.F32, L.stream())
+    ops.colsum(dpre[0:BT], eng.gate["t"].gb, accumulate=True)
+    ops.colsum(dpre[BT:], eng.gate["pv"].gb, accumulate=True)
+    dlo, clo = eng._lo(dpre), eng._lo(cc)
+    with (ops.grouped() if E.GROUP_GATE else contextlib.nullcontext()):
+        for m, (r0, r1) in (("t", (0, BT)), ("pv", (BT, Nt))):
+            eng.gate[m].dgrad(dlo[r0:r1], dx=dc[r0:r1], beta=1.0)
+            eng.gate[m].wgrad(dlo[r0:r1], clo[r0:r1], bias_done=True)
+    d_ind = torch.empty((Nt, H), **f32)
+    dXT = torch.empty((Nt, H), **f32)
+    L.call("k3m_relu_split2_bwd", dc.data_ptr(), cc.data_ptr(), d_ind.data_ptr(), dXT.data_ptr(), Nt, H, 0, L.F32,
+           L.stream())
+
+    # ---- encoder, reversed
+    if eng.enc_dtype != torch.float32:
+        dXT = ops.convert(dXT, torch.empty(dXT.shape, dtype=eng.enc_dtype, device=dev))
+    view = _views(eng, ctx["train"])
+    for kind, i, sv in reversed(ctx["enc"]):
+        if kind == "t":
+            dXT = view(eng.text[i]).bwd(dXT, sv)
+        else:
+            s, op = sv
+            dXT2 = torch.empty_like(dXT)
+            args = (dXT[BT:], dXT[0:BT], s, dXT2[BT:], dXT2[0:BT])
+            if E.GROUPED:
+                E._lockstep([op.bwd_steps(*args)])
+            else:
+                op.bwd(*args)
+            dXT = dXT2
+        if grad_ready is not None:
+            grad_ready(kind, i)
+
+    # ---- embeddings
+    ph = eng.p_h if ctx["train"] else 0.0
+    ops.convert(dXT, d_ind, accumulate=True)
+    xh, rs, off_t, off_p = ctx["emb"]
+    gword = fp.g["embeddings.word_embeddings.weight"]
+    gpos = fp.g["embeddings.position_embeddings.weight"]
+    gtyp = fp.g["embeddings.token_type_embeddings.weight"]
+    for r0, r1, off, ids, tt in ((0, BT, off_t, batch["input_ids"], batch["segment_ids"]),
+                                 (BT, Nt, off_p, batch["input_ids_pv"], batch["segment_ids_pv"])):
+        ds = torch.empty((r1 - r0, H), **f32)
+        ops.ln_bwd(d_ind[r0:r1], xh[r0:r1], rs[r0:r1], eng.emb_ln.g, ds, ds, eng.emb_ln.gg, eng.emb_ln.gb, p_out=ph,
+                   seed=ctx["seed"], off_out=off)
+        ops.embed_bwd(ids.contiguous(), tt.contiguous(), ds, gword, gpos, gtyp)
+    if grad_ready is not None:
+        grad_ready("emb", 0)

@@ -34,10 +34,23 @@ _ENGINE_NAMES = [("input_ids", "input_ids"), ("token_type_ids", "segment_ids"), 
                  ("image_feat", "image_feat"), ("image_loc", "image_loc"), ("image_attention_mask", "image_mask")]
 
 
-def stack_pair(pair, device):
-    """Pair batch (forward-argument names) -> the engine's stacked 2B batch."""
+def _is_image_arg(name):
+    return name.startswith("image_")
+
+
+def _pair_args(pair, use_image):
+    """The forward's arguments out of a pair dict.  Every one is required (KeyError), except the image arguments
+    of a model without the image modality, which may be left out."""
+    return {k: pair[k] for k in ARG_NAMES if use_image or not _is_image_arg(k) or k in pair}
+
+
+def stack_pair(pair, device, use_image=True):
+    """Pair batch (forward-argument names) -> the engine's stacked 2B batch.  use_image=False: the image
+    arguments (None or absent, as the reference passes them) are left out."""
     out = {}
     for src, dst in _ENGINE_NAMES:
+        if not use_image and _is_image_arg(src):
+            continue
         a, b = pair[src + "_1"], pair[src + "_2"]
         if a.shape[1:] != b.shape[1:]:
             raise ValueError("%s: items 1 and 2 differ in shape (%s vs %s)" % (src, tuple(a.shape), tuple(b.shape)))
@@ -69,15 +82,16 @@ class K3MForItemAlignment(object):
 
     def forward(self, *args, output_all_attention_masks=False, train=True, noise=None, seed=None, **kw):
         """Positional / keyword arguments as K3MForItemAlignment.forward.  noise: optional pair
-        (noise_item1, noise_item2) of {v,t,pv} gumbel-noise dicts (explicit randomness for parity)."""
+        (noise_item1, noise_item2) of {v,t,pv} gumbel-noise dicts (explicit randomness for parity).
+        With cfg.use_image false the image arguments may be None or left out ({t,pv} noise of 2 candidates)."""
         pair = dict(zip(ARG_NAMES, args))
         pair.update({k: v for k, v in kw.items() if k in ARG_NAMES})
-        missing = [k for k in ARG_NAMES if k not in pair]
+        eng = self.engine
+        missing = [k for k in ARG_NAMES if k not in pair and (eng.use_image or not _is_image_arg(k))]
         if missing:
             raise TypeError("missing arguments: %s" % missing)
-        eng = self.engine
         dev = eng.device
-        batch = stack_pair(pair, dev)
+        batch = stack_pair(pair, dev, eng.use_image)
         B = pair["input_ids_1"].shape[0]
         nz = None
         if noise is not None:
@@ -155,7 +169,7 @@ class ItemAlignmentTrainer(Trainer):
     def step(self, pair, noise=None):
         """One optimisation step on a pair batch (dict with the forward's argument names)."""
         eng = self.engine
-        e1, e2, probs, loss = self.model.forward(*[pair[k] for k in ARG_NAMES], train=True, noise=noise,
+        e1, e2, probs, loss = self.model.forward(**_pair_args(pair, eng.use_image), train=True, noise=noise,
                                                  seed=self.global_step)
         hook = self.ddp.grad_ready if self.ddp is not None else None
         if self.ddp is not None:
@@ -182,7 +196,7 @@ def evaluate(model, batches, thresholds=None):
         thresholds = np.arange(0.1, 1.0, 0.1)
     probs, labels = [], []
     for pair in batches:
-        _, _, p, _ = model.forward(*[pair[k] for k in ARG_NAMES], train=False)
+        _, _, p, _ = model.forward(**_pair_args(pair, model.engine.use_image), train=False)
         model._ctx = None   # no backward in evaluation
         probs.append(p.detach().float().cpu().numpy())
         labels.append(pair["labels"].detach().float().cpu().numpy())

@@ -24,6 +24,11 @@ frozen segment is never touched by the optimizer — exactly the reference's beh
 The never-grad set follows the fusion mode (``is_frozen(name, cfg)``): 86 tensors for
 ``if_pre_sampling`` 0 and 1, 80 for the soft gate (2: ``soft_*`` train), 104 for interactive-only
 (3: the ``score_*`` scorers are unused too).
+
+Without the image modality (``cfg.use_image`` false; vilbert_k3m.py:2202-2250, :2876-2923): 444 tensors
+(445 keys) for pretraining and 441 for item alignment, no ``v_*`` / ``c_layer`` / ``c_layer_pv_v`` / ``map_*`` /
+``*_v`` tensors, ``Linear(2H -> H)`` scorers; 36 / 34 never-grad tensors (``score_cross1_(t|pv)`` join the set:
+their cross-1 partner is the absent image) and ``[score_self_m | score_cross2_m]`` as the fused gate view.
 """
 import re
 
@@ -123,47 +128,54 @@ def param_spec(cfg):
 def _encoder_spec(cfg):
     H, I = cfg.hidden_size, cfg.intermediate_size
     Hv, Iv, Hb = cfg.v_hidden_size, cfg.v_intermediate_size, cfg.bi_hidden_size
+    use_image = getattr(cfg, "use_image", True)
     nco = len(cfg.v_biattention_id)
     s = []
     for i in range(cfg.num_hidden_layers):
         s += _bert_layer("encoder.layer.%d" % i, H, I)
-    for i in range(cfg.v_num_hidden_layers):
-        s += _bert_layer("encoder.v_layer.%d" % i, Hv, Iv)
+    if use_image:
+        for i in range(cfg.v_num_hidden_layers):
+            s += _bert_layer("encoder.v_layer.%d" % i, Hv, Iv)
     if cfg.with_coattention:
-        for i in range(nco):
-            s += _conn_layer("encoder.c_layer.%d" % i, Hv, H, Hb, Iv, I)
-        for i in range(nco):
-            s += _conn_layer("encoder.c_layer_pv_v.%d" % i, Hv, H, Hb, Iv, I)
+        if use_image:
+            for i in range(nco):
+                s += _conn_layer("encoder.c_layer.%d" % i, Hv, H, Hb, Iv, I)
+            for i in range(nco):
+                s += _conn_layer("encoder.c_layer_pv_v.%d" % i, Hv, H, Hb, Iv, I)
         for i in range(nco):
             s += _conn_layer("encoder.c_layer_pv_t.%d" % i, H, H, H, I, I)
     return s
 
 
 def item_alignment_spec(cfg):
-    """K3MForItemAlignment.named_parameters() (vilbert_k3m.py:2866-2950, use_image=True): module
-    registration order embeddings, v_embeddings, v_pooler, encoder, t_pooler, the fusion maps and
-    gates, classifier (loss_type "ce": ClassificationHead :2164-2183), struc_w1..3."""
-    if not getattr(cfg, "use_image", True):
-        raise NotImplementedError("item alignment without the image modality (use_image=False)")
+    """K3MForItemAlignment.named_parameters() (vilbert_k3m.py:2866-2950): module registration order
+    embeddings, v_embeddings, v_pooler, encoder, t_pooler, the fusion maps and gates, classifier
+    (loss_type "ce": ClassificationHead :2164-2183), struc_w1..3.  Without the image modality
+    (use_image=False) the v_* modules, the maps and the *_v gates are not registered and the text /
+    PV gates are Linear(2H -> H) (:2894-2923)."""
+    use_image = getattr(cfg, "use_image", True)
     H, V = cfg.hidden_size, cfg.vocab_size
     Hv, Hb = cfg.v_hidden_size, cfg.bi_hidden_size
     s = [("embeddings.word_embeddings.weight", (V, H)),
          ("embeddings.position_embeddings.weight", (cfg.max_position_embeddings, H)),
          ("embeddings.token_type_embeddings.weight", (cfg.type_vocab_size, H))]
     s += _ln("embeddings.LayerNorm", H)
-    s += _lin("v_embeddings.image_embeddings", Hv, cfg.v_feature_size)
-    s += _lin("v_embeddings.image_location_embeddings", Hv, 5)
-    s += _ln("v_embeddings.LayerNorm", Hv)
-    s += _lin("v_pooler.dense", Hb, Hv)
+    if use_image:
+        s += _lin("v_embeddings.image_embeddings", Hv, cfg.v_feature_size)
+        s += _lin("v_embeddings.image_location_embeddings", Hv, 5)
+        s += _ln("v_embeddings.LayerNorm", Hv)
+        s += _lin("v_pooler.dense", Hb, Hv)
     s += _encoder_spec(cfg)
     s += _lin("t_pooler.dense", Hb, H)
-    s += _lin("map_individual_to_bi", Hb, H)
-    s += _lin("map_bi_to_individual", H, Hb)
-    for n in ("score_self_v", "score_cross1_v", "score_cross2_v", "soft_v"):
-        s += _lin(n, Hb, 3 * Hb)
+    if use_image:
+        s += _lin("map_individual_to_bi", Hb, H)
+        s += _lin("map_bi_to_individual", H, Hb)
+        for n in ("score_self_v", "score_cross1_v", "score_cross2_v", "soft_v"):
+            s += _lin(n, Hb, 3 * Hb)
+    nm = 3 if use_image else 2
     for n in ("score_self_t", "score_cross1_t", "score_cross2_t", "soft_t",
               "score_self_pv", "score_cross1_pv", "score_cross2_pv", "soft_pv"):
-        s += _lin(n, H, 3 * H)
+        s += _lin(n, H, nm * H)
     if getattr(cfg, "loss_type", "ce") == "ce":
         s += _lin("classifier.dense", H, 2 * H) + _lin("classifier.out_proj", 2, H)
     s += _lin("struc_w1", H, 3 * H) + _lin("struc_w2", 1, H) + _lin("struc_w3", H, H)
@@ -176,6 +188,7 @@ _FROZEN_RE = re.compile(r"(\.q_dense[12]\.|^t_pooler\.|^v_pooler\.|^cls\.seq_rel
 
 _SOFT_RE = re.compile(r"^soft_(v|t|pv)\.")
 _SCORE_RE = re.compile(r"^score_(self|cross1|cross2)_(v|t|pv)\.")
+_CROSS1_RE = re.compile(r"^score_cross1_(t|pv)\.")
 
 
 def is_frozen(name, cfg=None):
@@ -187,8 +200,14 @@ def is_frozen(name, cfg=None):
     gate (2) uses ``soft_*``, so they train; interactive-only (3) uses neither ``soft_*`` nor the
     ``score_*`` scorers, so both are never-grad.  Pretraining model: 86 tensors in modes 0 and 1
     (and without ``cfg``), 80 in mode 2, 104 in mode 3.  Mode 0 keeps ``score_*`` trainable with a
-    zero gradient, as it always has."""
+    zero gradient, as it always has.
+
+    Without the image modality (``cfg.use_image`` false) the cross-1 partner of the text and PV streams is
+    the absent image, so ``score_cross1_(t|pv)`` never enter the two-candidate gate (:2331-2374 with
+    ``sequence_c1 = None``): 36 never-grad tensors in the pretraining model, 34 in item alignment."""
     mode = getattr(cfg, "if_pre_sampling", 1) if cfg is not None else 1
+    if cfg is not None and not getattr(cfg, "use_image", True) and _CROSS1_RE.search(name):
+        return True
     if mode == 2 and _SOFT_RE.search(name):
         return False
     if mode == 3 and _SCORE_RE.search(name):
@@ -240,9 +259,12 @@ def fused_groups(cfg):
             for i in range(len(cfg.v_biattention_id)):
                 add("encoder.%s.%d.biattention." % (k, i), ("query1", "key1", "value1"))
                 add("encoder.%s.%d.biattention." % (k, i), ("query2", "key2", "value2"))
-    mods = (["v"] if getattr(cfg, "use_image", True) else []) + ["t", "pv"]
-    for m in mods:
-        add("", ["score_self_%s" % m, "score_cross1_%s" % m, "score_cross2_%s" % m])
+    if getattr(cfg, "use_image", True):
+        for m in ("v", "t", "pv"):
+            add("", ["score_self_%s" % m, "score_cross1_%s" % m, "score_cross2_%s" % m])
+    else:   # two-candidate gate: the never-grad score_cross1_m lives in the frozen segment, outside the group
+        for m in ("t", "pv"):
+            add("", ["score_self_%s" % m, "score_cross2_%s" % m])
     return groups
 
 

@@ -68,6 +68,8 @@ def objective1_labels(batch):
     keep = ((batch["is_next"] + batch["is_next_pv_v"] + batch["is_next_pv_t"]) == 0).long().unsqueeze(1)
     out = dict(batch)
     for k in ("image_label", "lm_label_ids", "lm_label_ids_pv"):
+        if k not in batch:   # image_label: absent from a batch of the model without the image modality
+            continue
         v = batch[k] * keep
         out[k] = torch.where(v == 0, torch.full_like(v, -1), v)
     out.pop("_label_counts", None)

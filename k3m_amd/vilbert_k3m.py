@@ -77,10 +77,13 @@ class BertForMultiModalPreTraining_tri_stru(nn.Module):
         return {k: v.detach() for k, v in sd.items()}
 
     def load_state_dict(self, state_dict, strict=True):
+        from .checkpoint import check_modalities, check_shapes
         sd = {k[7:] if k.startswith("module.") else k: v for k, v in state_dict.items()}
+        check_modalities(self._names, sd)   # tri-modal file into a model without the image modality, or the reverse
         missing = [n for n in self._names if n not in sd]
         if strict and missing:
             raise KeyError("missing keys: %s" % missing[:8])
+        check_shapes(self.engine.fp, sd)   # before the first copy: a refused file leaves the parameters as they were
         with torch.no_grad():
             for n in self._names:
                 if n in sd:
@@ -164,19 +167,22 @@ class BertForMultiModalPreTraining_tri_stru(nn.Module):
             input_ids=ids, input_mask=d(attention_mask, ids),
             segment_ids=d(token_type_ids) if token_type_ids is not None else torch.zeros_like(ids),
             lm_label_ids=d(masked_lm_labels), is_next=d(next_sentence_label),
-            input_ids_pv=d(input_ids_pv), image_feat=d(image_feat).float(), image_loc=d(image_loc).float(),
-            image_target=d(image_target).float(), image_label=d(image_label),
+            input_ids_pv=d(input_ids_pv),
             lm_label_ids_pv=d(masked_lm_labels_pv), is_next_pv_v=d(next_sentence_label_pv_v),
             is_next_pv_t=d(next_sentence_label_pv_t), index_p=d(index_p), index_v=d(index_v))
         batch["input_mask_pv"] = d(attention_mask_pv, batch["input_ids_pv"])
         batch["segment_ids_pv"] = (d(token_type_ids_pv) if token_type_ids_pv is not None
                                    else torch.zeros_like(batch["input_ids_pv"]))
-        B, R = batch["image_feat"].shape[:2]
-        batch["image_mask"] = (d(image_attention_mask) if image_attention_mask is not None
-                               else torch.ones((B, R), dtype=torch.int64, device=dev))
+        if self.engine.use_image:
+            batch.update(image_feat=d(image_feat).float(), image_loc=d(image_loc).float(),
+                         image_target=d(image_target).float(), image_label=d(image_label))
+            B, R = batch["image_feat"].shape[:2]
+            batch["image_mask"] = (d(image_attention_mask) if image_attention_mask is not None
+                                   else torch.ones((B, R), dtype=torch.int64, device=dev))
+        # (without the image modality the image arguments may be None, as in the reference; they are not read)
         # labelled-row counts attached by the loaders (k3m_amd/loaders.py): no device->host sync
         n_m = getattr(masked_lm_labels, "_k3m_n_labels", None)
-        n_v = getattr(image_label, "_k3m_n_labels", None)
+        n_v = getattr(image_label, "_k3m_n_labels", None) if self.engine.use_image else 0
         if n_m is not None and n_v is not None:
             batch["_label_counts"] = (n_m, n_v)
         kw = {"noise": gumbel_noise, "ent_neg": ent_neg, "val_neg": val_neg}

@@ -21,7 +21,10 @@ Differences, each stated:
   ``--k3m_synthetic_regions SEED`` (region features for TSV rows), ``--k3m_no_shuffle``,
   ``--k3m_max_steps N``, ``--k3m_loss_log PATH`` (one JSON line per step), and the parity harness
   ``--k3m_parity_case NPZ``: every step feeds the fixture's recorded batch with its gumbel noise and LPM
-  negatives, dropout off (the golden vectors were recorded with model.eval(); tests/test_gpu_train_driver.py).
+  negatives, dropout off (the golden vectors were recorded with model.eval(); tests/test_gpu_train_driver.py);
+* ``--text_only``: the model without the image modality (``config.use_image = False``, the reference's
+  ``pretrain.py`` without ``--use_image``): title and property-value knowledge only, 445-key checkpoints.  The
+  loaders still produce the image fields; the engine does not read them.
 """
 import argparse
 import json
@@ -95,6 +98,9 @@ def get_parser(argv=None):
     p.add_argument("--k3m_max_steps", default=0, type=int)
     p.add_argument("--k3m_loss_log", default="", type=str)
     p.add_argument("--k3m_parity_case", default="", type=str)
+    p.add_argument("--text_only", action="store_true",
+                   help="train the model without the image modality (config.use_image = False): title + "
+                        "property-value knowledge only; the loaders' image fields are ignored")
     return p.parse_args(argv)
 
 
@@ -108,10 +114,14 @@ def _parity_inputs(path, dev):
     d = np.load(path, allow_pickle=False)
     batch = {k[3:]: torch.from_numpy(d[k]).to(dev) for k in d.files if k.startswith("in/")}
     B, T = batch["input_ids"].shape
-    P, R = batch["input_ids_pv"].shape[1], batch["image_feat"].shape[1]
+    P = batch["input_ids_pv"].shape[1]
     rng = np.random.default_rng(int(d["noise_seed"]))
+    if "image_feat" in batch:
+        shapes = [("v", (B, batch["image_feat"].shape[1], 3, 1024)), ("t", (B, T, 3, 768)), ("pv", (B, P, 3, 768))]
+    else:   # a case recorded without the image modality (tests/golden/make_text_only_golden.py): 2 candidates
+        shapes = [("t", (B, T, 2, 768)), ("pv", (B, P, 2, 768))]
     noise = {k: torch.from_numpy((-np.log(rng.standard_exponential(s))).astype(np.float32)).to(dev)
-             for k, s in [("v", (B, R, 3, 1024)), ("t", (B, T, 3, 768)), ("pv", (B, P, 3, 768))]}
+             for k, s in shapes}
     return batch, noise, torch.from_numpy(d["ent_neg"]).to(dev), torch.from_numpy(d["val_neg"]).to(dev), \
         int(d["mode"])
 
@@ -168,6 +178,8 @@ def main(argv=None):
     config.dynamic_attention = args.dynamic_attention
     config.if_pre_sampling = args.if_pre_sampling
     config.num_negative = args.num_negative
+    if args.text_only:
+        config.use_image = False
 
     parity = None
     if args.k3m_parity_case:
