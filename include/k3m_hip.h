@@ -266,6 +266,26 @@ int k3m_soft_scale(const void* c, const float* a, void* z, int rows, int d, int 
                    hipStream_t stream);
 int k3m_soft_scale_bwd(const void* dz, const void* c, const float* a, void* dc, float* dpre, void* dpre_bf16, int rows,
                        int d, int dtype, hipStream_t stream);
+/* Dynamic image attention (config.dynamic_attention, BertImageSelfAttention vilbert_k3m.py:572-601): the image
+ * layers' Q and K are scaled per sequence by g = 1 + sigmoid(z), z = dyLinear_{q|k}(masked mean of the text
+ * partner) from the ordinary GEMM.  x / dx / qkv / dqkv in `dtype` (fp32 or bf16) with a row stride in elements;
+ * mask (0/1 floats), pool, inv_count, z, dz fp32.  No atomics, fixed summation order (bit-reproducible).
+ * Vector accesses of 16 bytes: h (hv) and the row strides must be multiples of 4 (fp32) / 8 (bf16) and x, dx,
+ * qkv, dqkv, pool, dpool, z, dz 16-byte aligned; K3M_EINVAL otherwise, nothing is launched.
+ * pool_fwd: pool[s,:] = sum_t mask[s,t] x[s*len+t,:] / sum_t mask[s,t]; inv_count[s] = 1 / sum_t mask[s,t].  A
+ *   sequence with no kept token gets pool = 0 and inv_count = 0 (never a division by zero).
+ * pool_bwd: dx[s*len+t,:] += mask[s,t] * inv_count[s] * dpool[s,:].
+ * scale_fwd: qkv[s*rows+r, c] *= 1 + sigmoid(z[s,c]) for c < 2*hv (z is [nseq, 2*hv]; the V block is untouched).
+ * scale_bwd: qkv holds the gated Q'|K'; S[s,c] = sum_r dqkv*qkv; dz = S / g * sig * (1 - sig); then
+ *   dqkv[:, c < 2*hv] *= g in place (the gradient w.r.t. the ungated projections).                     */
+int k3m_dyn_pool_fwd(const void* x, long long ldx, const float* mask, float* pool, float* inv_count, int nseq, int len,
+                     int h, int dtype, hipStream_t stream);
+int k3m_dyn_pool_bwd(const float* dpool, const float* mask, const float* inv_count, void* dx, long long ldx, int nseq,
+                     int len, int h, int dtype, hipStream_t stream);
+int k3m_dyn_scale_fwd(void* qkv, long long ld, const float* z, int nseq, int rows, int hv, int dtype,
+                      hipStream_t stream);
+int k3m_dyn_scale_bwd(void* dqkv, long long ldd, const void* qkv, long long ldq, const float* z, float* dz, int nseq,
+                      int rows, int hv, int dtype, hipStream_t stream);
 /* if_pre_sampling == 3: out = (x1+x2)/2 ; backward: dx_k (+)= dout/2 (either dx_k may be NULL).  n % 4 == 0. */
 int k3m_mean2(const void* x1, const void* x2, void* out, long long n, int dtype, hipStream_t stream);
 int k3m_mean2_bwd(const void* dout, void* dx1, void* dx2, long long n, int accumulate, int dtype,

@@ -82,6 +82,10 @@ SIGNATURES = {
     "k3m_soft_scale_bwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "k3m_mean2": [vp, vp, vp, i64, i32, vp],
     "k3m_mean2_bwd": [vp, vp, vp, i64, i32, i32, vp],
+    "k3m_dyn_pool_fwd": [vp, i64, vp, vp, vp, i32, i32, i32, i32, vp],
+    "k3m_dyn_pool_bwd": [vp, vp, vp, vp, i64, i32, i32, i32, i32, vp],
+    "k3m_dyn_scale_fwd": [vp, i64, vp, i32, i32, i32, i32, vp],
+    "k3m_dyn_scale_bwd": [vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, vp],
     "k3m_seq_mean": [vp, i32, i32, i32, i32, f32, vp, i32, i32, vp],
     "k3m_seq_mean_bwd": [vp, i32, i32, i32, i32, f32, vp, i32, vp],
     "k3m_sa_gather": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],

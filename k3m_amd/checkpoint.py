@@ -79,6 +79,25 @@ def check_modalities(names, sd):
                          "%d keys) but this model is tri-modal; nothing was loaded" % len(sd))
 
 
+DYN_KEY = "encoder.v_layer.0.attention.self.dyLinear_q.weight"   # present exactly with dynamic image attention
+V_LAYER_KEY = "encoder.v_layer.0.attention.self.query.weight"
+
+
+def check_dynamic_attention(names, sd):
+    """Refuse a state dict with the dyLinear_* gates for a model built without dynamic_attention and the reverse,
+    before anything is copied: every other tensor name and shape agrees, so a non-strict load would silently drop
+    the gates (or leave them untrained) and run another model than the file's."""
+    model_has, file_has = DYN_KEY in set(names), DYN_KEY in sd
+    if file_has and not model_has:
+        raise ValueError("the state dict holds the dynamic-attention gates (encoder.v_layer.*.attention.self.dyLinear_*, "
+                         "%d keys) but this model was built without dynamic_attention; nothing was loaded" % len(sd))
+    # a file without image layers (an encoder-only BERT checkpoint for --pretrained_model_path) passes
+    if model_has and not file_has and V_LAYER_KEY in sd:
+        raise ValueError("this model was built with dynamic_attention=True but the state dict (%d keys) has image "
+                         "layers without the encoder.v_layer.*.attention.self.dyLinear_* gates; nothing was loaded"
+                         % len(sd))
+
+
 def check_shapes(fp, sd):
     """Every tensor of ``sd`` that the model has must have the model's shape (checked before the first copy)."""
     for name, _ in fp.spec:
@@ -91,6 +110,7 @@ def load_model_state_dict(fp, sd, strict=True):
     shapes are checked before the first copy: a refused file leaves the parameters as they were."""
     sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
     check_modalities([n for n, _ in fp.spec], sd)
+    check_dynamic_attention([n for n, _ in fp.spec], sd)
     missing = [n for n, _ in fp.spec if n not in sd]
     if strict and missing:
         raise KeyError("state_dict lacks %d parameters, e.g. %s" % (len(missing), missing[:4]))

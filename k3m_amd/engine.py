@@ -32,7 +32,7 @@ import torch
 from . import debug
 from . import _lib as L
 from . import ops
-from .params import flat_layout, frozen_names
+from .params import dynamic_attention, flat_layout, frozen_names
 
 EPS = 1e-12
 
@@ -229,11 +229,65 @@ def _attn_bwd(dctx, o, q, k, v, saved, dq, dk, dv):
         ops.attn_bwd(dctx, o, q, k, v, stat, dq, dk, dv, nseq, lq, lk, nh, hd, 1.0 / math.sqrt(hd), p, seed, off)
 
 
+class PoolGrad(object):
+    """The cross-stream gradient an image layer's backward hands to the engine: dpool, the gradient of the layer's
+    stacked text pools [n, H], with the masks and 1 / counts the pools were made with.  add_into() adds it into the
+    text-stream gradient rows the pools were read from."""
+
+    def __init__(self, dpool, inv_count, masks):
+        self.dpool, self.inv_count, self.masks = dpool, inv_count, masks
+
+    def add_into(self, dparts):
+        """dparts: views of the text-stream gradient rows, in partner order"""
+        r = 0
+        for m, dx in zip(self.masks, dparts):
+            ops.dyn_pool_bwd(self.dpool[r:r + m.shape[0]], m, self.inv_count[r:r + m.shape[0]], dx)
+            r += m.shape[0]
+
+
+class DynGate(object):
+    """Dynamic attention of an image layer (BertImageSelfAttention.forward, vilbert_k3m.py:592-601): the layer's Q
+    and K are scaled per sequence by 1 + sigmoid(dyLinear_{q|k}(masked mean of the text partner)).  dyLinear_q |
+    dyLinear_k are one [2 Hv, H] Linear; the pools of all the layer's sequences are stacked, so the gate GEMM, its
+    weight gradient and its input gradient are one launch each.  partner: [(text rows [n * L, H], mask [n, L] fp32
+    0/1)] in the order of the image buffer's sequences.  Kernels: k3m_amd/csrc/dynattn.hip."""
+
+    def __init__(self, fp, prefix):
+        self.lin = Lin(fp, [prefix + ".dyLinear_q", prefix + ".dyLinear_k"])
+
+    def gate(self, partner):
+        """pool kernels + the gate GEMM (fp32 in every mode); returns what scale() and the backward need"""
+        n = sum(m.shape[0] for _, m in partner)
+        dev = partner[0][0].device
+        pool = torch.empty((n, self.lin.W.shape[1]), dtype=torch.float32, device=dev)
+        ic = torch.empty((n,), dtype=torch.float32, device=dev)
+        r = 0
+        for xt, m in partner:
+            ops.dyn_pool_fwd(xt, m, pool[r:r + m.shape[0]], ic[r:r + m.shape[0]])
+            r += m.shape[0]
+        z = self.lin.fwd(pool)
+        return (pool, ic, z, [m for _, m in partner])
+
+    def scale(self, qkv, dsv):
+        z = dsv[2]
+        ops.dyn_scale_fwd(qkv, z, qkv.shape[0] // z.shape[0])
+
+    def bwd(self, dqkv, qkv, dsv):
+        """dqkv: gradient w.r.t. the gated Q'|K' (and V) -> w.r.t. the ungated projections, in place; accumulates
+        the dyLinear gradients; returns the gradient of the stacked pools as a PoolGrad."""
+        pool, ic, z, masks = dsv
+        dz = ops.dyn_scale_bwd(dqkv, qkv, z, torch.empty_like(z), qkv.shape[0] // z.shape[0])
+        self.lin.wgrad(dz, pool)
+        return PoolGrad(self.lin.dgrad(dz), ic, masks)
+
+
 class BertLayerOp(object):
     """BertLayer / BertImageLayer (vilbert_k3m.py:535-548, :696-709) over a wide buffer whose rows
-    hold several sequence segments [(row0, nseq, L, mask)]."""
+    hold several sequence segments [(row0, nseq, L, mask)].  dyn: an image layer's DynGate (dynamic attention);
+    its forward takes the text partner and its backward hands back the pool gradient (dyn_out)."""
 
-    def __init__(self, fp, prefix, nh, p_attn, p_hidden):
+    def __init__(self, fp, prefix, nh, p_attn, p_hidden, dyn=False):
+        self.dyn = DynGate(fp, prefix + ".attention.self") if dyn else None
         self.qkv = Lin(fp, [prefix + ".attention.self.query", prefix + ".attention.self.key",
                             prefix + ".attention.self.value"])
         self.o = Lin(fp, prefix + ".attention.output.dense")
@@ -241,9 +295,13 @@ class BertLayerOp(object):
         self.ffn = FFN(fp, prefix + ".intermediate", prefix + ".output", p_hidden)
         self.nh, self.p_attn = nh, p_attn
 
-    def fwd(self, x, segs, rng):
+    def fwd(self, x, segs, rng, partner=None):
         M, H = x.shape
         qkv = self.qkv.fwd(x)
+        dsv = None
+        if self.dyn is not None:
+            dsv = self.dyn.gate(partner)
+            self.dyn.scale(qkv, dsv)
         ctx = torch.empty((M, H), dtype=x.dtype, device=x.device)
         asv = []
         with ops.branches():   # the sequence segments (text 36, PV 128) are independent launches
@@ -255,10 +313,10 @@ class BertLayerOp(object):
         a = self.o.fwd(ctx)
         h1, tsv = self.tail.fwd(a, x, rng)
         y, fsv = self.ffn.fwd(h1, rng)
-        return y, (x, qkv, ctx, asv, tsv, fsv, segs)
+        return y, (x, qkv, ctx, asv, tsv, fsv, segs, dsv)
 
-    def bwd(self, dy, saved):
-        x, qkv, ctx, asv, tsv, fsv, segs = saved
+    def bwd(self, dy, saved, dyn_out=None):
+        x, qkv, ctx, asv, tsv, fsv, segs, dsv = saved
         M, H = x.shape
         dh1 = self.ffn.bwd(dy, fsv)
         dx = torch.empty_like(x)
@@ -271,16 +329,21 @@ class BertLayerOp(object):
                 r1 = r0 + nseq * ln
                 ops.branch(_attn_bwd, dctx[r0:r1], ctx[r0:r1], qkv[r0:r1, 0:H], qkv[r0:r1, H:2 * H], qkv[r0:r1, 2 * H:],
                            s, dqkv[r0:r1, 0:H], dqkv[r0:r1, H:2 * H], dqkv[r0:r1, 2 * H:])
+        if dsv is not None:
+            dyn_out.append(self.dyn.bwd(dqkv, qkv, dsv))
         self.qkv.wgrad(dqkv, x)
         self.qkv.dgrad(dqkv, dx=dx, beta=1.0)
         return dx
 
 
     # lock-step form (see ConnectionOp.fwd_steps): segments end at the GEMM stages
-    def fwd_steps(self, x, segs, rng, res):
+    def fwd_steps(self, x, segs, rng, res, partner=None):
         M, H = x.shape
         qkv = self.qkv.fwd(x)
+        dsv = self.dyn.gate(partner) if self.dyn is not None else None
         yield
+        if dsv is not None:
+            self.dyn.scale(qkv, dsv)
         ctx = torch.empty((M, H), dtype=x.dtype, device=x.device)
         asv = []
         for (r0, nseq, ln, mask) in segs:
@@ -297,16 +360,22 @@ class BertLayerOp(object):
         o = self.ffn.o.fwd(f)
         yield
         y, ts2 = self.ffn.tail.fwd(o, h1, rng)
-        res.append((y, (x, qkv, ctx, asv, tsv, (h1, u, f, ts2), segs)))
+        res.append((y, (x, qkv, ctx, asv, tsv, (h1, u, f, ts2), segs, dsv)))
 
-    def bwd_steps(self, dy, saved, res):
-        x, qkv, ctx, asv, tsv, fsv, segs = saved
+    def bwd_steps(self, dy, saved, res, exact=False, dyn_out=None):
+        """res: [dx].  dyn_out: as in bwd(), receives a layer with dynamic attention's PoolGrad (the GEMM that
+        writes it is pending until the lock step's last flush).  exact: keep the bits of bwd().  One product differs otherwise: the
+        dGELU input gradient leaves the bias gradient's column sums as 32-row slabs from its epilogue, and a grouped
+        launch sums a slab's rows in the order of the tile the whole group runs on, so intermediate.dense.bias
+        moves in its last bit; that GEMM is then launched on its own, as bwd() launches it."""
+        x, qkv, ctx, asv, tsv, fsv, segs, dsv = saved
         M, H = x.shape
         h1, u, f, ts2 = fsv
         dh1 = torch.empty_like(h1)
         do = self.ffn.tail.bwd(dy, ts2, dh1, dxsum=self.ffn.o.gb)
         self.ffn.o.wgrad(do, f, bias_done=True)
-        du = self.ffn.o.dgrad(do, dgelu_aux=u, colsum_out=self.ffn.i.gb)
+        with (ops.ungrouped() if exact else contextlib.nullcontext()):
+            du = self.ffn.o.dgrad(do, dgelu_aux=u, colsum_out=self.ffn.i.gb)
         yield
         self.ffn.i.wgrad(du, h1, bias_done=True)
         self.ffn.i.dgrad(du, dx=dh1, beta=1.0)
@@ -321,6 +390,8 @@ class BertLayerOp(object):
             r1 = r0 + nseq * ln
             _attn_bwd(dctx[r0:r1], ctx[r0:r1], qkv[r0:r1, 0:H], qkv[r0:r1, H:2 * H], qkv[r0:r1, 2 * H:], sv,
                       dqkv[r0:r1, 0:H], dqkv[r0:r1, H:2 * H], dqkv[r0:r1, 2 * H:])
+        if dsv is not None:
+            dyn_out.append(self.dyn.bwd(dqkv, qkv, dsv))
         self.qkv.wgrad(dqkv, x)
         self.qkv.dgrad(dqkv, dx=dx, beta=1.0)
         res.append(dx)
@@ -519,11 +590,14 @@ class K3MEngine(object):
         c = cfg
         assert getattr(c, "fixed_t_layer", 0) == 0 and getattr(c, "fixed_v_layer", 0) == 0
         assert not getattr(c, "in_batch_pairs", False) and not getattr(c, "fast_mode", False)
-        assert not getattr(c, "dynamic_attention", False) and getattr(c, "model", "bert") in ("bert", "roberta")
+        assert getattr(c, "model", "bert") in ("bert", "roberta")
         assert c.with_coattention
         assert getattr(c, "visual_target", 0) == 0
         # False: the model without the image modality — the forward / backward pair of k3m_amd/engine_text.py
         self.use_image = bool(getattr(c, "use_image", True))
+        # dynamic image attention (cfg.dynamic_attention; nothing to gate without the image modality): every
+        # image layer's Q and K are scaled by a gate computed from its text partner (DynGate)
+        self.dyn_attn = dynamic_attention(c)
         self.H, self.Hv, self.Hb = c.hidden_size, c.v_hidden_size, c.bi_hidden_size
         self.p_h = c.hidden_dropout_prob
         self.p_a = c.attention_probs_dropout_prob
@@ -537,7 +611,8 @@ class K3MEngine(object):
                                    self.p_h, self.p_h) for i in range(nco)]
         self.emb_ln = LN(fp, "embeddings.LayerNorm")
         if self.use_image:
-            self.image = [BertLayerOp(fp, "encoder.v_layer.%d" % i, c.v_num_attention_heads, self.p_va, self.p_vh)
+            self.image = [BertLayerOp(fp, "encoder.v_layer.%d" % i, c.v_num_attention_heads, self.p_va, self.p_vh,
+                                      dyn=self.dyn_attn)
                           for i in range(c.v_num_hidden_layers)]
             self.co_tv = [ConnectionOp(fp, "encoder.c_layer.%d" % i, nb, self.p_va, self.p_a, self.p_vh, self.p_h,
                                        self.p_vh, self.p_h) for i in range(nco)]
@@ -700,15 +775,22 @@ class K3MEngine(object):
         # ---- encoder, lock-step wide passes
         tsegs = [(0, 2 * B, T, mask_t2), (2 * BT, 2 * B, P, mask_p2)]
         vsegs = [(0, 2 * B, R, mask_v2)]
+        if self.dyn_attn:   # 0/1 masks of the image streams' text partners: the title (pass 1), the PV (pass 2)
+            mt01, mp01 = mt.to(torch.float32).contiguous(), mp.to(torch.float32).contiguous()
+
+        def partner(xt):
+            return [(xt[0:BT], mt01), (xt[2 * BT:2 * BT + BP], mp01)] if self.dyn_attn else None
         enc = []
         sched = list(self.schedule)
         si = 0
         while si < len(sched):
             kind, i = sched[si]
             nxt = sched[si + 1] if si + 1 < len(sched) else None
-            if GROUP_TV and nxt is not None and {kind, nxt[0]} == {"t", "v"}:
+            if GROUP_TV and nxt is not None and {kind, nxt[0]} == {"t", "v"} and not (self.dyn_attn and kind == "t"):
                 # a text layer and an image layer at the same schedule position are independent:
-                # run them in lock step so their GEMM stages share grouped launches
+                # run them in lock step so their GEMM stages share grouped launches.  With dynamic attention the
+                # image layer reads the text stream: independent only where the image layer comes first (after the
+                # last co-attention block; both then read the text state from before the pair)
                 pair = [(kind, i), nxt]
                 gens, outs = [], []
                 for k_, j_ in pair:
@@ -717,7 +799,10 @@ class K3MEngine(object):
                         op = _eval_view(op)
                     r = []
                     outs.append(r)
-                    gens.append(op.fwd_steps(XT if k_ == "t" else XV, tsegs if k_ == "t" else vsegs, rng, r))
+                    if k_ == "t":
+                        gens.append(op.fwd_steps(XT, tsegs, rng, r))
+                    else:
+                        gens.append(op.fwd_steps(XV, vsegs, rng, r, partner=partner(XT)))
                 _lockstep(gens)
                 for (k_, j_), r in zip(pair, outs):
                     y, sv = r[0]
@@ -739,7 +824,7 @@ class K3MEngine(object):
                 op = self.image[i]
                 if not train:
                     op = _eval_view(op)
-                XV, sv = op.fwd(XV, vsegs, rng)
+                XV, sv = op.fwd(XV, vsegs, rng, partner=partner(XT))
                 enc.append((kind, i, sv))
             else:
                 XT2 = torch.empty_like(XT)
@@ -1199,26 +1284,36 @@ class K3MEngine(object):
             dXT = ops.convert(dXT, torch.empty(dXT.shape, dtype=self.enc_dtype, device=dev))
             dXV = ops.convert(dXV, torch.empty(dXV.shape, dtype=self.enc_dtype, device=dev))
         renc = list(reversed(ctx["enc"]))
+
+        def dparts(dxt):   # the text-stream gradient rows the image layers' pools were taken from
+            return [dxt[0:BT], dxt[2 * BT:2 * BT + BP]]
         ei = 0
         while ei < len(renc):
             kind, i, sv = renc[ei]
             nxt = renc[ei + 1] if ei + 1 < len(renc) else None
-            if GROUP_TV and nxt is not None and {kind, nxt[0]} == {"t", "v"}:
-                gens, outs = [], []
+            if GROUP_TV and nxt is not None and {kind, nxt[0]} == {"t", "v"} and not (self.dyn_attn and kind == "v"):
+                # (the pairs of the forward.)  Dynamic attention: the image layer's pool gradient belongs to the
+                # text state BEFORE the pair, i.e. to the gradient this text layer's backward produces: added below
+                gens, outs, pool_grads = [], [], []
                 for k_, j_, sv_ in (renc[ei], nxt):
                     op = self.text[j_] if k_ == "t" else self.image[j_]
                     if not ctx["train"]:
                         op = _eval_view(op)
                     r = []
                     outs.append(r)
-                    gens.append(op.bwd_steps(dXT if k_ == "t" else dXV, sv_, r))
+                    # with dynamic attention the paired step keeps the unpaired step's bits (exact)
+                    gens.append(op.bwd_steps(dXT if k_ == "t" else dXV, sv_, r, exact=self.dyn_attn,
+                                             dyn_out=pool_grads))
                 _lockstep(gens)
                 for (k_, j_, _), r in zip((renc[ei], nxt), outs):
                     if k_ == "t":
                         dXT = r[0]
                     else:
                         dXV = r[0]
-                    if grad_ready is not None:
+                for pg in pool_grads:   # the image layer's, into the dXT the paired text layer just produced
+                    pg.add_into(dparts(dXT))
+                if grad_ready is not None:
+                    for k_, j_, _ in (renc[ei], nxt):
                         grad_ready(k_, j_)
                 ei += 2
                 continue
@@ -1228,7 +1323,10 @@ class K3MEngine(object):
                 dXT = op.bwd(dXT, sv)
             elif kind == "v":
                 op = self.image[i] if ctx["train"] else _eval_view(self.image[i])
-                dXV = op.bwd(dXV, sv)
+                pool_grads = []
+                dXV = op.bwd(dXV, sv, dyn_out=pool_grads)
+                for pg in pool_grads:   # before any earlier text op consumes these rows of dXT
+                    pg.add_into(dparts(dXT))
             else:
                 s_tv, s_pv, s_tt, ops_ = sv
                 dXT2 = torch.empty_like(dXT)

@@ -183,7 +183,8 @@ class StepGraphs(object):
         return (tr.ddp is None and tr.accum_steps == 1 and tr.micro == 0 and tr.ADAMW is None
                 and tr.lr_schedule == "warmup_linear" and tr.objective != 1 and batch.get("_label_counts") is not None
                 and tr.engine.fp.data.is_cuda
-                and tr.engine.use_image)   # the step without the image modality is not captured: eager
+                and tr.engine.use_image   # the step without the image modality is not captured: eager
+                and not tr.engine.dyn_attn)   # nor is the step with dynamic image attention
 
     def _capture(self, batch, key):
         self.tr.engine.check_hints()   # a completed label-count check that failed raises before any update

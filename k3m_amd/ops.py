@@ -86,6 +86,20 @@ class grouped(object):
         return False
 
 
+class ungrouped(object):
+    """Inside ``with grouped():`` — launch the GEMMs issued in this block at once, each on its own, instead of
+    deferring them to the group (a product whose bits must not depend on what it shares a launch with)."""
+
+    def __enter__(self):
+        global _grouper
+        self.prev, _grouper = _grouper, None
+
+    def __exit__(self, *exc):
+        global _grouper
+        _grouper = self.prev
+        return False
+
+
 class branches(object):
     """Context manager for independent launches on side streams: ``branch(fn, ...)`` inside runs fn
     with a pool stream current (waiting first on everything the main stream issued before the
@@ -653,3 +667,41 @@ def scatter_add_rows(src, idx, n, dst):
         _debug.check_range(idx[:n], 0, dst.shape[0], "scatter_add_rows index")
     call("k3m_scatter_add_rows", ptr(src), _ld(src), ptr(idx), n, src.shape[1], ptr(dst), _ld(dst), dt(src),
          stream())
+
+
+# ------------------------------------------------------------------ dynamic image attention (dynattn.hip)
+def dyn_pool_fwd(x, mask, pool, inv_count):
+    """pool [nseq, H] fp32 = masked mean over the L rows of each sequence of x [nseq * L, H] (fp32 / bf16 row view);
+    mask [nseq, L] fp32 0/1; inv_count [nseq] fp32 = 1 / kept tokens (0 for a sequence with none: its pool is 0)."""
+    nseq, ln = mask.shape
+    assert x.shape[0] == nseq * ln and pool.shape == (nseq, x.shape[1]) and pool.is_contiguous()
+    assert mask.dtype == torch.float32 and mask.is_contiguous() and inv_count.numel() == nseq
+    call("k3m_dyn_pool_fwd", ptr(x), _ld(x), ptr(mask), ptr(pool), ptr(inv_count), nseq, ln, x.shape[1], dt(x), stream())
+    return pool
+
+
+def dyn_pool_bwd(dpool, mask, inv_count, dx):
+    """dx [nseq * L, H] += mask * inv_count * dpool (row-broadcast), the backward of dyn_pool_fwd."""
+    nseq, ln = mask.shape
+    assert dx.shape[0] == nseq * ln and dpool.shape == (nseq, dx.shape[1]) and dpool.is_contiguous()
+    assert dpool.dtype == torch.float32 and mask.dtype == torch.float32 and mask.is_contiguous()
+    call("k3m_dyn_pool_bwd", ptr(dpool), ptr(mask), ptr(inv_count), ptr(dx), _ld(dx), nseq, ln, dx.shape[1], dt(dx),
+         stream())
+
+
+def dyn_scale_fwd(qkv, z, rows):
+    """qkv [nseq * rows, >= 2 Hv] (the fused q|k|v buffer): its first 2 Hv columns *= 1 + sigmoid(z[seq]), in place."""
+    nseq, hv2 = z.shape
+    assert qkv.shape[0] == nseq * rows and qkv.shape[1] >= hv2 and z.dtype == torch.float32 and z.is_contiguous()
+    call("k3m_dyn_scale_fwd", ptr(qkv), _ld(qkv), ptr(z), nseq, rows, hv2 // 2, dt(qkv), stream())
+
+
+def dyn_scale_bwd(dqkv, qkv, z, dz, rows):
+    """dz [nseq, 2 Hv] fp32 from the gradient dqkv w.r.t. the gated Q'|K' and the saved gated qkv; then scales the
+    Q and K blocks of dqkv by the gate in place (gradient w.r.t. the ungated projections)."""
+    nseq, hv2 = z.shape
+    assert dqkv.shape == qkv.shape and qkv.shape[0] == nseq * rows and qkv.shape[1] >= hv2 and dqkv.dtype == qkv.dtype
+    assert z.dtype == torch.float32 and z.is_contiguous() and dz.shape == z.shape and dz.is_contiguous()
+    call("k3m_dyn_scale_bwd", ptr(dqkv), _ld(dqkv), ptr(qkv), _ld(qkv), ptr(z), ptr(dz), nseq, rows, hv2 // 2, dt(qkv),
+         stream())
+    return dz

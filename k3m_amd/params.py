@@ -46,9 +46,13 @@ def _ln(prefix, n):
     return [(prefix + ".weight", (n,)), (prefix + ".bias", (n,))]
 
 
-def _bert_layer(p, H, I):
+def _bert_layer(p, H, I, dyn_in=0):
+    """dyn_in > 0: a BertImageLayer with dynamic attention (vilbert_k3m.py:572-574) — dyLinear_q / dyLinear_k,
+    Linear(dyn_in -> H), registered right after value."""
+    dyn = (_lin(p + ".attention.self.dyLinear_q", H, dyn_in) + _lin(p + ".attention.self.dyLinear_k", H, dyn_in)
+           if dyn_in else [])
     return (_lin(p + ".attention.self.query", H, H) + _lin(p + ".attention.self.key", H, H)
-            + _lin(p + ".attention.self.value", H, H) + _lin(p + ".attention.output.dense", H, H)
+            + _lin(p + ".attention.self.value", H, H) + dyn + _lin(p + ".attention.output.dense", H, H)
             + _ln(p + ".attention.output.LayerNorm", H) + _lin(p + ".intermediate.dense", I, H)
             + _lin(p + ".output.dense", H, I) + _ln(p + ".output.LayerNorm", H))
 
@@ -71,6 +75,12 @@ def _conn_layer(p, H1, H2, Hb, I1, I2):
     return s
 
 
+def dynamic_attention(cfg):
+    """True when the image layers carry the dyLinear_* gates: cfg.dynamic_attention on a model with the image
+    modality (without it the reference builds no v_layer, vilbert_k3m.py:1138-1141, and the flag changes nothing)."""
+    return bool(getattr(cfg, "dynamic_attention", False)) and bool(getattr(cfg, "use_image", True))
+
+
 def param_spec(cfg):
     """Ordered [(name, shape)] exactly as the reference ``named_parameters()``; ``cfg.task``
     selects the model: "pretrain" (BertForMultiModalPreTraining_tri_stru, default) or
@@ -89,7 +99,7 @@ def param_spec(cfg):
         s += _bert_layer("encoder.layer.%d" % i, H, I)
     if use_image:
         for i in range(cfg.v_num_hidden_layers):
-            s += _bert_layer("encoder.v_layer.%d" % i, Hv, Iv)
+            s += _bert_layer("encoder.v_layer.%d" % i, Hv, Iv, dyn_in=H if dynamic_attention(cfg) else 0)
     if cfg.with_coattention:
         if use_image:
             for i in range(nco):
@@ -135,7 +145,7 @@ def _encoder_spec(cfg):
         s += _bert_layer("encoder.layer.%d" % i, H, I)
     if use_image:
         for i in range(cfg.v_num_hidden_layers):
-            s += _bert_layer("encoder.v_layer.%d" % i, Hv, Iv)
+            s += _bert_layer("encoder.v_layer.%d" % i, Hv, Iv, dyn_in=H if dynamic_attention(cfg) else 0)
     if cfg.with_coattention:
         if use_image:
             for i in range(nco):
@@ -253,6 +263,8 @@ def fused_groups(cfg):
     if getattr(cfg, "use_image", True):
         for i in range(cfg.v_num_hidden_layers):
             add("encoder.v_layer.%d.attention.self." % i, qkv)
+            if dynamic_attention(cfg):   # the two gate projections as one [2Hv, H] Linear
+                add("encoder.v_layer.%d.attention.self." % i, ("dyLinear_q", "dyLinear_k"))
     if cfg.with_coattention:
         kinds = (["c_layer", "c_layer_pv_v"] if getattr(cfg, "use_image", True) else []) + ["c_layer_pv_t"]
         for k in kinds:
