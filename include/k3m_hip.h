@@ -210,6 +210,13 @@ int k3m_ce_fwd_bwd(float* logits, long long ld, const int64_t* labels, const flo
  * sum_c xlogy(t,t) - t*logsoftmax(pred); pred overwritten by scale*(softmax*sum(t) - t). */
 int k3m_kl_fwd_bwd(float* logits, long long ld, const float* target, long long ldt, const int32_t* trow,
                    const float* row_scale, int rows, int ncls, float* loss_rows, hipStream_t stream);
+/* Region feature regression (visual_target 1: MSELoss(reduction="none"), :2232-2237, :2745-2752) over gathered
+ * rows, one workgroup per row: loss_rows[r] = (1/ncols) * sum_c (pred[r,c] - target[trow[r],c])^2; pred is
+ * overwritten by row_scale[r] * (2/ncols) * (pred - target) (exact zeros where row_scale[r] == 0).  16-byte
+ * accesses when ncols, ld, ldt are multiples of 4 and both pointers are 16-byte aligned, scalar otherwise.
+ * rows == 0 returns 0 without a launch; ncols <= 0, ld < ncols, ldt < ncols or a null pointer is K3M_EINVAL. */
+int k3m_mse_fwd_bwd(float* pred, long long ld, const float* target, long long ldt, const int32_t* trow,
+                    const float* row_scale, int rows, int ncols, float* loss_rows, hipStream_t stream);
 /* x[r][c] *= (slot[r] == 0 ? w0 : w1): the shared MLM decoder's gradient rows of the text (slot 0) and PV
  * (slot 1) heads weighted by their losses' upstream gradients (a caller's w_t*mlm_t + w_pv*mlm_pv; the
  * reference sums them with weight 1, train_concap_struc.py:531-533). */

@@ -1,5 +1,6 @@
 // Loss kernels of the pretraining heads: label compaction, masked-LM cross-entropy and region KL
-// (forward and gradient in one pass over the logits row), per-task loss reduction, NSP forward.
+// (forward and gradient in one pass over the logits row), region feature regression (MSE), per-task loss
+// reduction, NSP forward.
 #include "common.h"
 
 namespace {
@@ -111,6 +112,43 @@ __global__ __launch_bounds__(256) void kl_kernel(float* __restrict__ logits, lon
   }
 }
 
+// --- region feature regression (visual_target 1): mean_c (x - t)^2, one streaming pass ------------
+// VEC: 16-byte loads and stores (the host checked ncols, ld, ldt and both pointers); the gradient does not
+// depend on the row sum, so x and t are read once and x is written once.  A row with rscale 0 (padding past
+// the device count) gets an exact-zero gradient whatever it holds.
+template <bool VEC>
+__global__ __launch_bounds__(256) void mse_kernel(float* __restrict__ pred, long long ld, const float* __restrict__ tgt,
+                                                  long long ldt, const int32_t* __restrict__ trow,
+                                                  const float* __restrict__ rscale, int ncols,
+                                                  float* __restrict__ loss_rows) {
+  __shared__ float red[4];
+  const int r = blockIdx.x;
+  float* x = pred + (long long)r * ld;
+  const float* t = tgt + (long long)trow[r] * ldt;
+  const float sc = rscale[r];
+  const float k = sc * (2.f / (float)ncols);
+  float s = 0.f;
+  if (VEC) {
+    for (int c = threadIdx.x * 4; c < ncols; c += 1024) {
+      const floatx4 xv = *reinterpret_cast<const floatx4*>(x + c);
+      const floatx4 tv = *reinterpret_cast<const floatx4*>(t + c);
+      const floatx4 d = xv - tv;
+      s += d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3];
+      floatx4 g = d * k;
+      if (sc == 0.f) g = floatx4{0.f, 0.f, 0.f, 0.f};
+      *reinterpret_cast<floatx4*>(x + c) = g;
+    }
+  } else {
+    for (int c = threadIdx.x; c < ncols; c += 256) {
+      const float d = x[c] - t[c];
+      s += d * d;
+      x[c] = sc == 0.f ? 0.f : d * k;
+    }
+  }
+  s = block_sum<4>(s, red);
+  if (threadIdx.x == 0) loss_rows[r] = s * (1.f / (float)ncols);
+}
+
 // gradient rows of the text / PV MLM heads (slot 0 / 1 of the shared decoder's labelled rows) weighted by their
 // losses' upstream gradients, which differ only when a caller weights mlm_t and mlm_pv differently
 __global__ __launch_bounds__(256) void scale_rows_slot_kernel(float* __restrict__ x, long long ld,
@@ -194,6 +232,22 @@ extern "C" int k3m_kl_fwd_bwd(float* logits, long long ld, const float* target, 
   if (rows == 0) return 0;
   hipLaunchKernelGGL(kl_kernel, dim3(rows), dim3(256), 0, st, logits, ld, target, ldt, trow, row_scale, ncls,
                      loss_rows);
+  K3M_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int k3m_mse_fwd_bwd(float* pred, long long ld, const float* target, long long ldt, const int32_t* trow,
+                               const float* row_scale, int rows, int ncols, float* loss_rows, hipStream_t st) {
+  if (rows == 0) return 0;
+  K3M_ARG(pred && target && trow && row_scale && loss_rows && rows > 0 && ncols > 0 && ld >= ncols && ldt >= ncols);
+  const bool vec = ncols % 4 == 0 && ld % 4 == 0 && ldt % 4 == 0 && ((uintptr_t)pred & 15) == 0 &&
+                   ((uintptr_t)target & 15) == 0;
+  if (vec)
+    hipLaunchKernelGGL(mse_kernel<true>, dim3(rows), dim3(256), 0, st, pred, ld, target, ldt, trow, row_scale, ncols,
+                       loss_rows);
+  else
+    hipLaunchKernelGGL(mse_kernel<false>, dim3(rows), dim3(256), 0, st, pred, ld, target, ldt, trow, row_scale, ncols,
+                       loss_rows);
   K3M_CHECK_LAUNCH();
   return 0;
 }

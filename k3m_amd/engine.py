@@ -558,6 +558,14 @@ def validate_config(cfg):
         raise ValueError("use_image=False with if_pre_sampling=%s: the reference defines only the hard gate "
                          "(if_pre_sampling=1) for the model without the image modality"
                          % getattr(cfg, "if_pre_sampling", 1))
+    # masked-region objective: 0 = KL against the detector's class probabilities, 1 = MSE regression of the
+    # region's own feature (vilbert_k3m.py:2232-2237, :2745-2752)
+    vt = getattr(cfg, "visual_target", 0)
+    if vt == 2:
+        raise ValueError("visual_target=2 (NCE) is not built: the reference's own forward fails for it, reading "
+                         "self.num_negative, which no constructor sets (vilbert_k3m.py:2764-2765)")
+    if vt not in (0, 1):
+        raise ValueError("visual_target=%r: the reference defines 0 (KL), 1 (feature regression) and 2 (NCE)" % (vt,))
 
 
 class K3MEngine(object):
@@ -592,7 +600,7 @@ class K3MEngine(object):
         assert not getattr(c, "in_batch_pairs", False) and not getattr(c, "fast_mode", False)
         assert getattr(c, "model", "bert") in ("bert", "roberta")
         assert c.with_coattention
-        assert getattr(c, "visual_target", 0) == 0
+        self.visual_target = int(getattr(c, "visual_target", 0))
         # False: the model without the image modality — the forward / backward pair of k3m_amd/engine_text.py
         self.use_image = bool(getattr(c, "use_image", True))
         # dynamic image attention (cfg.dynamic_attention; nothing to gate without the image modality): every
@@ -1049,15 +1057,20 @@ class K3MEngine(object):
         lv = self.img_dec.fwd(hlv)
         if self.capture_logits:
             captured["img_logits"] = lv.clone()
+        if batch["image_target"].numel() != B * R1 * Cv:   # e.g. class probabilities fed to visual_target 1
+            raise ValueError("image_target: shape %s, expected %s for visual_target=%d"
+                             % (tuple(batch["image_target"].shape), (B, R1, Cv), self.visual_target))
         tgt = batch["image_target"].reshape(B * R1, Cv).contiguous()
         lr_v = torch.empty((n_v,), dtype=torch.float32, device=dev)
-        L.call("k3m_kl_fwd_bwd", lv.data_ptr(), Cv, tgt.data_ptr(), Cv, src_v.data_ptr(), sc_v.data_ptr(), n_v, Cv,
-               lr_v.data_ptr(), L.stream())
+        # visual_target 1: mean squared error against the region's own feature (:2745-2752) in place of the KL
+        L.call("k3m_mse_fwd_bwd" if self.visual_target == 1 else "k3m_kl_fwd_bwd", lv.data_ptr(), Cv, tgt.data_ptr(),
+               Cv, src_v.data_ptr(), sc_v.data_ptr(), n_v, Cv, lr_v.data_ptr(), L.stream())
         if n_v:
             L.call("k3m_loss_reduce", lr_v.data_ptr(), sc_v.data_ptr(), sl_v.data_ptr(), n_v, losses.data_ptr(),
                    L.stream())
-        else:
+        elif self.visual_target == 0:
             losses[2] = float("nan")   # 0/0 as in the reference (:2758-2760)
+        # else: the regression's denominator is clamped at 1 (:2750-2752), so no masked region gives 0.0
         ctx["img"] = (idx_v, n_v, hv, pre_v, hlv, xh_iv, rs_iv, lv)
 
         nsp = torch.empty((1,), dtype=torch.float32, device=dev)

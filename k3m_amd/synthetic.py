@@ -59,7 +59,10 @@ def synthetic_batch(cfg, batch_size, device, seed=1234, T=36, P=128, n_boxes=36,
     y1, y2 = xy[:, :, 0, 1], xy[:, :, 1, 1]
     loc = torch.stack([x1, y1, x2, y2, (x2 - x1) * (y2 - y1)], 2)
     loc = torch.cat([torch.tensor([0.0, 0.0, 1.0, 1.0, 1.0]).expand(B, 1, 5), loc], 1)
-    tgt = torch.softmax(torch.randn((B, n_boxes, cfg.v_target_size), generator=g), -1)
+    if getattr(cfg, "visual_target", 0) == 0:   # the detector's class probabilities
+        tgt = torch.softmax(torch.randn((B, n_boxes, cfg.v_target_size), generator=g), -1)
+    else:   # the regions' own features before any masking (dataset:584-601); the global region is not a target
+        tgt = feat[:, 1:].clone()
     lab = torch.full((B, n_boxes), -1, dtype=torch.int64)
     pk = torch.rand((B, n_boxes), generator=g) < 0.15
     pk[torch.arange(B), torch.randint(0, n_boxes, (B,), generator=g)] = True
