@@ -38,6 +38,8 @@ enum K3mEpilogue {
   K3M_EPI_NONE = 0,         /* C = alpha*acc + beta*C                                        */
   K3M_EPI_BIAS = 1,         /* C = alpha*(acc + bias) + beta*C                               */
   K3M_EPI_BIAS_GELU = 2,    /* aux = acc + bias; C = gelu(aux)            (BertIntermediate)  */
+                            /* aux == NULL: forward-only, C = gelu(acc + bias) and nothing   */
+                            /* else (a kernel form without the store; same C, bit for bit)   */
   K3M_EPI_DGELU = 3,        /* C = acc * gelu'(aux) (+ beta*C)            (its backward)      */
   K3M_EPI_BIAS_SIGMOID = 4  /* C = sigmoid(acc + bias)                    (fusion gate scores)*/
 };
@@ -103,7 +105,9 @@ int k3m_slab_reduce_batch(const float* const* ws, float* const* out, const int* 
 /* Post-LN residual block tail (BertSelfOutput/BertOutput/BertBiOutput/BertImageEmbeddings,
  * vilbert_k3m.py:485-489, :528-532, :986-996, :2153-2161, LayerNorm :319-332):
  *   s = dropout_in(x) + res;  y = dropout_out(gamma * (s-mean)*rstd + beta)
- * saves xhat = (s-mean)*rstd and rstd for the backward.  res may be NULL. */
+ * saves xhat = (s-mean)*rstd and rstd for the backward.  res may be NULL.
+ * xhat == NULL && rstd == NULL: the forward-only form (a kernel instantiation without those stores; y is
+ * bit-identical); one of the two NULL alone is an argument error. */
 int k3m_ln_fwd(const void* x, const void* res, const float* gamma, const float* beta, void* y, void* xhat,
                float* rstd, int rows, int cols, float eps, float p_in, float p_out, uint64_t seed,
                uint64_t off_in, uint64_t off_out, int dtype, hipStream_t stream);
@@ -140,7 +144,8 @@ int k3m_embed_bwd(const int64_t* ids, const int64_t* tt, const void* ds, float* 
  * dropout (BertSelfAttention :439-475, BertImageSelfAttention :586-634, BertBiAttention :753-838,
  * BertBiAttention_two_text :882-965).  Row (s, i) of Q starts at q + (s*lq+i)*ldq; head h is
  * columns [h*hd, (h+1)*hd).  kmask: additive float [nseq, lk].  probs: [nseq, nh, lq, lk]
- * (softmax output before dropout), saved for the backward. */
+ * (softmax output before dropout), saved for the backward.  probs == NULL (k3m_attn_fwd and k3m_attn_long_fwd):
+ * the forward-only form, kernel instantiations without the [nseq, nh, lq, lk] store; ctx is bit-identical. */
 int k3m_attn_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv,
                  const float* kmask, void* ctx, long long ldc, float* probs, int nseq, int lq, int lk, int nh, int hd,
                  float scale, float p_drop, uint64_t seed, uint64_t off, int dtype, hipStream_t stream);
@@ -154,7 +159,8 @@ int k3m_attn_bwd(const void* dctx, long long ldc, const void* o, long long ldo, 
 /* bf16 attention for the mixed-precision encoder (same semantics as k3m_attn_fwd/bwd; head dim
  * 64, 96 or 128, L <= 128): instead of the [nseq, nh, lq, lk] probabilities the forward saves the row
  * log-sum-exp lse [nseq, nh, lq] and the backward recomputes P from it (kmask is needed again).
- * Every row pointer + ld must allow 16-byte loads (ld % 8 == 0, 16-B aligned base). */
+ * Every row pointer + ld must allow 16-byte loads (ld % 8 == 0, 16-B aligned base).
+ * lse == NULL (k3m_flash_attn_fwd and k3m_flash_attn_long_fwd): the forward-only form, no LSE store. */
 int k3m_flash_attn_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv,
                        const float* kmask, void* ctx, long long ldc, float* lse, int nseq, int lq, int lk, int nh,
                        int hd, float scale, float p_drop, uint64_t seed, uint64_t off, hipStream_t stream);

@@ -106,7 +106,7 @@ class BertConfig(object):
 
 
 def pretrain_config(path, with_coattention=True, if_pre_sampling=1, visual_target=0,
-                    dynamic_attention=False, num_negative=255, use_image=True):
+                    dynamic_attention=False, num_negative=255, use_image=True, fixed_t_layer=0):
     """Load a JSON config and apply the pretraining driver's mutations
     (train_concap_struc.py:184, :198-211).  use_image=False: the model without the image modality
     (title + property-value knowledge only; the reference's pretrain.py --use_image left off)."""
@@ -118,11 +118,12 @@ def pretrain_config(path, with_coattention=True, if_pre_sampling=1, visual_targe
     cfg.dynamic_attention = dynamic_attention
     cfg.if_pre_sampling = if_pre_sampling
     cfg.num_negative = num_negative
+    cfg.fixed_t_layer = fixed_t_layer   # text layers 0 .. fixed_t_layer - 1 run without a backward (:206-207)
     return cfg
 
 
 def finetune_config(path, loss_type="ce", use_image=True, with_coattention=True, if_pre_sampling=1, visual_target=0,
-                    dynamic_attention=False, num_negative_image=255):
+                    dynamic_attention=False, num_negative_image=255, fixed_t_layer=0):
     """Load a JSON config and apply the fine-tuning driver's mutations (finetune.py:1307-1322):
     model "roberta" (whose embeddings behave as BERT's — BertEmbeddings.forward ignores the
     position ids RobertaEmbeddings passes, vilbert_k3m.py:361-367, :394-408), loss_type, use_image."""
@@ -137,4 +138,5 @@ def finetune_config(path, loss_type="ce", use_image=True, with_coattention=True,
     cfg.num_negative_image = num_negative_image
     cfg.loss_type = loss_type
     cfg.task = "item_alignment"
+    cfg.fixed_t_layer = fixed_t_layer   # finetune.py:1318-1319
     return cfg

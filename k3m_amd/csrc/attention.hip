@@ -173,7 +173,9 @@ __device__ __forceinline__ void chunk_dots(float* __restrict__ dst, const Chunks
 }
 
 // ------------------------------------------------------------------ forward
-template <typename T, int ML, int NW>
+// SAVE = false (here and in the two register-softmax forwards below): the forward-only form of k3m_attn_fwd with
+// probs == NULL, chosen per launch on the host: the kernel holds no store to probs; ctx is bit-identical
+template <typename T, int ML, int NW, bool SAVE = true>
 __global__ __launch_bounds__(NW * 64, ML == 64 ? 3 : 1) void attn_fwd_kernel(const T* __restrict__ q, long long ldq, const T* __restrict__ k,
                                                        long long ldk, const T* __restrict__ v, long long ldv,
                                                        const float* __restrict__ kmask, T* __restrict__ ctx,
@@ -282,13 +284,17 @@ __global__ __launch_bounds__(NW * 64, ML == 64 ? 3 : 1) void attn_fwd_kernel(con
         const float e0 = x0[u] * inv;
         const bool ok0 = lane < lk;
         const float pd0 = ok0 ? e0 * k3m_attn_drop(dr, off, rbase + i, lk, lane) : 0.f;
-        if (ok0) probs[prow + lane] = e0;
+        if constexpr (SAVE) {
+          if (ok0) probs[prow + lane] = e0;
+        }
         if (lane < LK) Ss[sw(i, lane, LK)] = pd0;
         if (TWO) {
           const float e1 = x1[u] * inv;
           const bool ok1 = lane + 64 < lk;
           const float pd1 = ok1 ? e1 * k3m_attn_drop(dr, off, rbase + i, lk, lane + 64) : 0.f;
-          if (ok1) probs[prow + lane + 64] = e1;
+          if constexpr (SAVE) {
+            if (ok1) probs[prow + lane + 64] = e1;
+          }
           if (lane + 64 < LK) Ss[sw(i, lane + 64, LK)] = pd1;
         }
       }
@@ -508,7 +514,7 @@ __device__ __forceinline__ float4 keep4(bool ok, float4 x) {
 //                  compile-time offsets;
 //   ctx            lane (q, kl) holds O[q][32dt + crow(r, kl)]: 16-byte stores.
 // No S or P image in LDS, one barrier per workgroup.  crow(r, kl) = (r & 3) + 8 (r >> 2) + 4 kl.
-template <int HD>
+template <int HD, bool SAVE = true>
 __global__ __launch_bounds__(256, 2) void attn_fwd_reg_kernel(const float* __restrict__ q, long long ldq,
                                                               const float* __restrict__ k, long long ldk,
                                                               const float* __restrict__ v, long long ldv,
@@ -648,7 +654,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_reg_kernel(const float* __res
 #ifdef K3M_LAB_NO_PSTORE   // lab only (scripts/lab/lab_build.sh): the forward without its probability stores
           if (false) {
 #else
-          if (qok) {
+          if (SAVE && qok) {
 #endif
             if (vec && j0 < lk) {
               *reinterpret_cast<float4*>(probs + prow + j0) = make_float4(p4[0], p4[1], p4[2], p4[3]);
@@ -750,7 +756,7 @@ __device__ __forceinline__ void x6_mma(floatx16& acc, const x6bf16x8& ah, const 
 
 __host__ __device__ constexpr int x6_lkp(int LK) { return LK <= 32 ? 32 : LK <= 64 ? 64 : 128; }
 
-template <int HD>
+template <int HD, bool SAVE = true>
 __global__ __launch_bounds__(256, 2) void attn_fwd_x6_kernel(const float* __restrict__ q, long long ldq,
                                                              const float* __restrict__ k, long long ldk,
                                                              const float* __restrict__ v, long long ldv,
@@ -920,7 +926,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_x6_kernel(const float* __rest
 #ifdef K3M_LAB_NO_PSTORE   // lab only (scripts/lab/lab_build.sh): the forward without its probability stores
           if (false) {
 #else
-          if (qok) {
+          if (SAVE && qok) {
 #endif
             if (vec && j0 < lk) {
               *reinterpret_cast<float4*>(probs + prow + j0) = make_float4(p4[0], p4[1], p4[2], p4[3]);
@@ -1563,7 +1569,8 @@ template <typename T, int ML, int NW>
 void set_lds_attr() {
   static bool done = false;
   if (!done) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<T, ML, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<T, ML, NW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<T, ML, NW, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
     (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<T, ML, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
     done = true;
   }
@@ -1574,9 +1581,14 @@ void launch_fwd(const void* q, long long ldq, const void* k, long long ldk, cons
                 const float* kmask, void* ctx, long long ldc, float* probs, int nseq, int lq, int lk, int nh, int hd,
                 float scale, float p_drop, uint64_t seed, uint64_t off, size_t lds, hipStream_t st) {
   set_lds_attr<T, ML, NW>();
-  hipLaunchKernelGGL((attn_fwd_kernel<T, ML, NW>), dim3(nseq * nh), dim3(NW * 64), lds, st, (const T*)q, ldq,
-                     (const T*)k, ldk, (const T*)v, ldv, kmask, (T*)ctx, ldc, probs, lq, lk, nh, hd, scale, p_drop,
-                     seed, off);
+  if (probs)
+    hipLaunchKernelGGL((attn_fwd_kernel<T, ML, NW, true>), dim3(nseq * nh), dim3(NW * 64), lds, st, (const T*)q, ldq,
+                       (const T*)k, ldk, (const T*)v, ldv, kmask, (T*)ctx, ldc, probs, lq, lk, nh, hd, scale, p_drop,
+                       seed, off);
+  else
+    hipLaunchKernelGGL((attn_fwd_kernel<T, ML, NW, false>), dim3(nseq * nh), dim3(NW * 64), lds, st, (const T*)q, ldq,
+                       (const T*)k, ldk, (const T*)v, ldv, kmask, (T*)ctx, ldc, probs, lq, lk, nh, hd, scale, p_drop,
+                       seed, off);
 }
 
 template <typename T, int ML, int NW>
@@ -1599,23 +1611,23 @@ static const bool kAttnFwdReg = k3m_env_flag("K3M_ATTN_FWD_REG", true);
 // the f32-MFMA register kernel
 static const bool kAttnX6 = k3m_env_flag("K3M_ATTN_X6", true);
 
-template <int HD>
+template <int HD, bool SAVE>
 void launch_fwd_reg(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv,
                     const float* kmask, void* ctx, long long ldc, float* probs, int nseq, int lq, int lk, int nh,
                     float scale, float p_drop, uint64_t seed, uint64_t off, hipStream_t st) {
   static bool done = false;
   if (!done) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_reg_kernel<HD>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-    (void)hipFuncSetAttribute((const void*)attn_fwd_x6_kernel<HD>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)attn_fwd_reg_kernel<HD, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)attn_fwd_x6_kernel<HD, SAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
     done = true;
   }
   if (kAttnX6) {
-    hipLaunchKernelGGL(attn_fwd_x6_kernel<HD>, dim3(nseq * nh), dim3(256), fwd_x6_lds(lk, HD), st, (const float*)q,
+    hipLaunchKernelGGL((attn_fwd_x6_kernel<HD, SAVE>), dim3(nseq * nh), dim3(256), fwd_x6_lds(lk, HD), st, (const float*)q,
                        ldq, (const float*)k, ldk, (const float*)v, ldv, kmask, (float*)ctx, ldc, probs, lq, lk, nh, scale,
                        p_drop, seed, off);
     return;
   }
-  hipLaunchKernelGGL(attn_fwd_reg_kernel<HD>, dim3(nseq * nh), dim3(256), fwd_reg_lds(lk, HD), st, (const float*)q, ldq,
+  hipLaunchKernelGGL((attn_fwd_reg_kernel<HD, SAVE>), dim3(nseq * nh), dim3(256), fwd_reg_lds(lk, HD), st, (const float*)q, ldq,
                      (const float*)k, ldk, (const float*)v, ldv, kmask, (float*)ctx, ldc, probs, lq, lk, nh, scale, p_drop,
                      seed, off);
 }
@@ -1624,7 +1636,7 @@ extern "C" int k3m_attn_fwd(const void* q, long long ldq, const void* k, long lo
                             const float* kmask, void* ctx, long long ldc, float* probs, int nseq, int lq, int lk,
                             int nh, int hd, float scale, float p_drop, uint64_t seed, uint64_t off, int dtype,
                             hipStream_t st) {
-  K3M_ARG(q && k && v && ctx && probs);
+  K3M_ARG(q && k && v && ctx);   // probs == NULL: the forward-only form
   K3M_ARG(lq > 0 && lq <= MAXL && lk > 0 && lk <= MAXL && hd > 0 && hd <= MAXD && hd % 32 == 0 && nh > 0);
   if (nseq == 0) return 0;
   K3M_ARG(vec_ok(q, ldq, dtype) && vec_ok(k, ldk, dtype) && vec_ok(v, ldv, dtype));
@@ -1635,9 +1647,15 @@ extern "C" int k3m_attn_fwd(const void* q, long long ldq, const void* k, long lo
   const int LK = (lk + 31) & ~31;
   if (dtype == K3M_F32 && kAttnFwdReg && (hd == 64 || hd == 96 || hd == 128) && LK * hd <= 8192 &&
       vec_ok(ctx, ldc, dtype) && (reinterpret_cast<uintptr_t>(probs) & 15) == 0) {
-    if (hd == 64) launch_fwd_reg<64>(q, ldq, k, ldk, v, ldv, kmask, ctx, ldc, probs, nseq, lq, lk, nh, scale, p_drop, seed, off, st);
-    else if (hd == 96) launch_fwd_reg<96>(q, ldq, k, ldk, v, ldv, kmask, ctx, ldc, probs, nseq, lq, lk, nh, scale, p_drop, seed, off, st);
-    else launch_fwd_reg<128>(q, ldq, k, ldk, v, ldv, kmask, ctx, ldc, probs, nseq, lq, lk, nh, scale, p_drop, seed, off, st);
+#define K3M_FWD_REG(HD_)                                                                                              \
+  do {                                                                                                               \
+    if (probs) launch_fwd_reg<HD_, true>(q, ldq, k, ldk, v, ldv, kmask, ctx, ldc, probs, nseq, lq, lk, nh, scale, p_drop, seed, off, st);  \
+    else launch_fwd_reg<HD_, false>(q, ldq, k, ldk, v, ldv, kmask, ctx, ldc, probs, nseq, lq, lk, nh, scale, p_drop, seed, off, st);       \
+  } while (0)
+    if (hd == 64) K3M_FWD_REG(64);
+    else if (hd == 96) K3M_FWD_REG(96);
+    else K3M_FWD_REG(128);
+#undef K3M_FWD_REG
     K3M_CHECK_LAUNCH();
     return 0;
   }

@@ -59,7 +59,8 @@ __device__ __forceinline__ void stage(uint16_t* img, const uint16_t* __restrict_
 // waves 0-1 on head 2p, waves 2-3 on head 2p + 1, so every wave has queries and a workgroup's one memory round
 // trip stages two heads (one head per workgroup left two of its four waves idle and doubled the number of
 // latency-bound workgroups).  Image row 64 hh + r holds row r of head hh; the key mask is the sequence's, shared.
-template <int HD, bool PAIR = false>
+// SAVE = false: the forward-only form (k3m_flash_attn_fwd with lse == NULL), no store to lse in the kernel
+template <int HD, bool PAIR = false, bool SAVE = true>
 __global__ __launch_bounds__(NT, 2) void flash_fwd_kernel(const uint16_t* __restrict__ q, long long ldq,
                                                           const uint16_t* __restrict__ k, long long ldk,
                                                           const uint16_t* __restrict__ v, long long ldv,
@@ -167,7 +168,9 @@ __global__ __launch_bounds__(NT, 2) void flash_fwd_kernel(const uint16_t* __rest
   sum += __shfl_xor(sum, 32, 64);
   const float inv = 1.f / sum;
   const long long prow = ((long long)s * nh + h) * lq + i;   // row of the [nseq, nh, lq] LSE
-  if (kl == 0 && i < lq) lse[prow] = mx * kLn2 + __logf(sum);
+  if constexpr (SAVE) {
+    if (kl == 0 && i < lq) lse[prow] = mx * kLn2 + __logf(sum);
+  }
   if (p_drop > 0.f) {
     // registers 4 q + b of tile jt are keys 32 jt + 8 q + 4 kl + b: pairs (b = 0, 1), (2, 3) share one draw, pair
     // counter pb + 16 jt + 4 q + b / 2 (k3m_attn_drop), the high word mixed once (and once more for a carry)
@@ -652,6 +655,10 @@ void set_attrs() {
     (void)hipFuncSetAttribute((const void*)flash_fwd_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
     (void)hipFuncSetAttribute((const void*)flash_fwd_kernel<96>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
     (void)hipFuncSetAttribute((const void*)flash_fwd_kernel<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)flash_fwd_kernel<64, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)flash_fwd_kernel<128, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)flash_fwd_kernel<96, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)flash_fwd_kernel<64, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
     (void)hipFuncSetAttribute((const void*)flash_bwd_kernel<96>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
     (void)hipFuncSetAttribute((const void*)flash_bwd_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
     (void)hipFuncSetAttribute((const void*)flash_bwd_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
@@ -679,7 +686,7 @@ extern "C" int k3m_flash_attn_fwd(const void* q, long long ldq, const void* k, l
                                   long long ldv, const float* kmask, void* ctx, long long ldc, float* lse, int nseq,
                                   int lq, int lk, int nh, int hd, float scale, float p_drop, uint64_t seed,
                                   uint64_t off, hipStream_t st) {
-  K3M_ARG(q && k && v && ctx && lse);
+  K3M_ARG(q && k && v && ctx);   // lse == NULL: the forward-only form
   K3M_ARG(lq > 0 && lq <= MAXL && lk > 0 && lk <= MAXL && (hd == 64 || hd == 96 || hd == 128) && nh > 0 && nseq >= 0);
   K3M_ARG(vec_ok(q, ldq) && vec_ok(k, ldk) && vec_ok(v, ldv));
   if (nseq == 0) return 0;
@@ -690,15 +697,21 @@ extern "C" int k3m_flash_attn_fwd(const void* q, long long ldq, const void* k, l
   K3M_ARG(lds <= (size_t)LDS_MAX);
   set_attrs();
   const int nblk = nseq * (pair ? (nh + 1) / 2 : nh);
-#define K3M_FLASH_FWD(HD_, P_)                                                                                   \
-  hipLaunchKernelGGL((flash_fwd_kernel<HD_, P_>), dim3(nblk), dim3(NT), lds, st, (const uint16_t*)q, ldq,           \
+#define K3M_FLASH_FWD_S(HD_, P_, S_)                                                                             \
+  hipLaunchKernelGGL((flash_fwd_kernel<HD_, P_, S_>), dim3(nblk), dim3(NT), lds, st, (const uint16_t*)q, ldq,           \
                      (const uint16_t*)k, ldk, (const uint16_t*)v, ldv, kmask, (uint16_t*)ctx, ldc, lse, lq, lk, nh, \
                      scale, p_drop, seed, off)
+#define K3M_FLASH_FWD(HD_, P_)           \
+  do {                                   \
+    if (lse) K3M_FLASH_FWD_S(HD_, P_, true); \
+    else K3M_FLASH_FWD_S(HD_, P_, false);    \
+  } while (0)
   if (hd == 96) K3M_FLASH_FWD(96, false);
   else if (hd == 64) {
     if (pair) K3M_FLASH_FWD(64, true); else K3M_FLASH_FWD(64, false);
   } else K3M_FLASH_FWD(128, false);
 #undef K3M_FLASH_FWD
+#undef K3M_FLASH_FWD_S
   K3M_CHECK_LAUNCH();
   return 0;
 }

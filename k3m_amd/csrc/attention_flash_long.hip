@@ -49,7 +49,8 @@ template <int HD> struct Geo {
 };
 
 // ------------------------------------------------------------------ forward
-template <int HD>
+// SAVE = false (both forwards): the forward-only form (lse == NULL), no store to lse in the kernel
+template <int HD, bool SAVE = true>
 __global__ __launch_bounds__(FNT, 2) void flash_long_fwd_kernel(const uint16_t* __restrict__ q, long long ldq,
                                                                 const uint16_t* __restrict__ k, long long ldk,
                                                                 const uint16_t* __restrict__ v, long long ldv,
@@ -177,7 +178,9 @@ __global__ __launch_bounds__(FNT, 2) void flash_long_fwd_kernel(const uint16_t* 
   if (!wact) return;
   const float lt = lp + __shfl_xor(lp, 32, 64);
   const float inv = 1.f / lt;
-  if (kl == 0 && iv) lse[prow] = m2 * LN2 + __logf(lt);
+  if constexpr (SAVE) {
+    if (kl == 0 && iv) lse[prow] = m2 * LN2 + __logf(lt);
+  }
   if (iv) {
     // O^T register r of tile dt: head dim 32 dt + (r & 3) + 8 (r >> 2) + 4 kl -> 4 consecutive dims per 8-B store
     uint16_t* op = ctx + (qrow0 + i) * ldc + hoff + 4 * kl;
@@ -761,7 +764,7 @@ template <int HD> constexpr int fwd2_occ() { return HD == 64 ? 3 : 2; }
 
 // DROP: the p > 0 form (a template parameter rather than a wave-uniform branch around two element loops: the d = 64
 // dropout form needs 150 VGPRs instead of the whole 168 of three waves per SIMD)
-template <int HD, bool DROP>
+template <int HD, bool DROP, bool SAVE = true>
 __global__ __launch_bounds__(FNT, fwd2_occ<HD>()) void flash_long_fwd2_kernel(
     const uint16_t* __restrict__ q, long long ldq, const uint16_t* __restrict__ k, long long ldk,
     const uint16_t* __restrict__ v, long long ldv, const float* __restrict__ kmask, uint16_t* __restrict__ ctx,
@@ -914,7 +917,9 @@ __global__ __launch_bounds__(FNT, fwd2_occ<HD>()) void flash_long_fwd2_kernel(
   if (!wact) return;
   const float lt = lp + __shfl_xor(lp, 32, 64);
   const float inv = 1.f / lt;
-  if (kl == 0 && iv) lse[prow] = m2 * LN2 + __logf(lt);
+  if constexpr (SAVE) {
+    if (kl == 0 && iv) lse[prow] = m2 * LN2 + __logf(lt);
+  }
   if (iv) {
     uint16_t* op = ctx + (qrow0 + i) * ldc + hoff + 4 * kl;
 #pragma unroll
@@ -1039,6 +1044,21 @@ void set_attrs() {
                               LDS_MAX);
     (void)hipFuncSetAttribute((const void*)flash_long_bwd2_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)flash_long_fwd_kernel<64, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)flash_long_fwd2_kernel<64, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)flash_long_fwd2_kernel<64, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)flash_long_fwd_kernel<96, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)flash_long_fwd2_kernel<96, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)flash_long_fwd2_kernel<96, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)flash_long_fwd_kernel<128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)flash_long_fwd2_kernel<128, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)flash_long_fwd2_kernel<128, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              LDS_MAX);
     done = true;
   }
 }
@@ -1051,7 +1071,7 @@ extern "C" int k3m_flash_attn_long_fwd(const void* q, long long ldq, const void*
                                        long long ldv, const float* kmask, void* ctx, long long ldc, float* lse, int nseq,
                                        int lq, int lk, int nh, int hd, float scale, float p_drop, uint64_t seed,
                                        uint64_t off, hipStream_t st) {
-  K3M_ARG(q && k && v && ctx && lse);
+  K3M_ARG(q && k && v && ctx);   // lse == NULL: the forward-only form
   K3M_ARG(lq > 0 && lq <= LMAX && lk > 0 && lk <= LMAX && (hd == 64 || hd == 96 || hd == 128) && nh > 0 && nseq >= 0);
   K3M_ARG(vec_ok(q, ldq) && vec_ok(k, ldk) && vec_ok(v, ldv) && vec_ok(ctx, ldc));
   if (nseq == 0) return 0;
@@ -1063,25 +1083,37 @@ extern "C" int k3m_flash_attn_long_fwd(const void* q, long long ldq, const void*
     const size_t lds2 = fwd2_lds(lk, hd);
     const bool drop = p_drop > 0.f;   // k3m_drop_init: thr != 0 iff p > 0
     const int xcdmap = kFlashLongXcd && (nseq * nh) % 8 == 0 ? 1 : 0;
-#define K3M_FL_FWD2(HD_, DR_)                                                                                     \
-    hipLaunchKernelGGL((flash_long_fwd2_kernel<HD_, DR_>), grid, dim3(FNT), lds2, st, (const uint16_t*)q, ldq,   \
+#define K3M_FL_FWD2_S(HD_, DR_, S_)                                                                               \
+    hipLaunchKernelGGL((flash_long_fwd2_kernel<HD_, DR_, S_>), grid, dim3(FNT), lds2, st, (const uint16_t*)q, ldq,   \
                        (const uint16_t*)k, ldk, (const uint16_t*)v, ldv, kmask, (uint16_t*)ctx, ldc, lse, lq, lk, nh, \
                        scale, p_drop, seed, off, xcdmap)
+#define K3M_FL_FWD2(HD_, DR_)                \
+    do {                                     \
+      if (lse) K3M_FL_FWD2_S(HD_, DR_, true);  \
+      else K3M_FL_FWD2_S(HD_, DR_, false);     \
+    } while (0)
     if (hd == 64) { if (drop) K3M_FL_FWD2(64, true); else K3M_FL_FWD2(64, false); }
     else if (hd == 96) { if (drop) K3M_FL_FWD2(96, true); else K3M_FL_FWD2(96, false); }
     else { if (drop) K3M_FL_FWD2(128, true); else K3M_FL_FWD2(128, false); }
 #undef K3M_FL_FWD2
+#undef K3M_FL_FWD2_S
     K3M_CHECK_LAUNCH();
     return 0;
   }
-#define K3M_FL_FWD(HD_)                                                                                           \
-  hipLaunchKernelGGL(flash_long_fwd_kernel<HD_>, grid, dim3(FNT), lds, st, (const uint16_t*)q, ldq,                \
+#define K3M_FL_FWD_S(HD_, S_)                                                                                     \
+  hipLaunchKernelGGL((flash_long_fwd_kernel<HD_, S_>), grid, dim3(FNT), lds, st, (const uint16_t*)q, ldq,                \
                      (const uint16_t*)k, ldk, (const uint16_t*)v, ldv, kmask, (uint16_t*)ctx, ldc, lse, lq, lk, nh, \
                      scale, p_drop, seed, off)
+#define K3M_FL_FWD(HD_)               \
+  do {                                \
+    if (lse) K3M_FL_FWD_S(HD_, true);   \
+    else K3M_FL_FWD_S(HD_, false);      \
+  } while (0)
   if (hd == 64) K3M_FL_FWD(64);
   else if (hd == 96) K3M_FL_FWD(96);
   else K3M_FL_FWD(128);
 #undef K3M_FL_FWD
+#undef K3M_FL_FWD_S
   K3M_CHECK_LAUNCH();
   return 0;
 }

@@ -56,7 +56,8 @@ __device__ __forceinline__ void stage(float* __restrict__ dst, const T* __restri
 __device__ __forceinline__ int acc_row(int r, int kl) { return (r & 3) + 8 * (r >> 2) + 4 * kl; }
 
 // ------------------------------------------------------------------ forward
-template <typename T>
+// SAVE = false: the forward-only form (probs == NULL), no store to probs in the kernel
+template <typename T, bool SAVE = true>
 __global__ __launch_bounds__(NT) void long_fwd_kernel(const T* __restrict__ q, long long ldq, const T* __restrict__ k,
                                                       long long ldk, const T* __restrict__ v, long long ldv,
                                                       const float* __restrict__ kmask, T* __restrict__ ctx, long long ldc,
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(NT) void long_fwd_kernel(const T* __restrict__ q, l
         float pd = 0.f;
         if (act && j < lk) {
           const float p = x[u] * inv;
-          probs[prow + j] = p;
+          if constexpr (SAVE) probs[prow + j] = p;
           pd = p * k3m_attn_dropout_scale(seed, p_drop, off, rbase + i0 + i, lk, j);
         }
         Ss[sw(i, j, LKP)] = pd;
@@ -307,11 +308,23 @@ void set_attrs() {
   static bool done = false;
   if (!done) {
     const int mx = 160 * 1024;
-    (void)hipFuncSetAttribute((const void*)long_fwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
+    (void)hipFuncSetAttribute((const void*)long_fwd_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
+    (void)hipFuncSetAttribute((const void*)long_fwd_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
     (void)hipFuncSetAttribute((const void*)long_bwd_q_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
     (void)hipFuncSetAttribute((const void*)long_bwd_kv_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
     done = true;
   }
+}
+
+// SAVE: the probability-saving kernel, or the forward-only instantiation
+template <typename T, bool SAVE>
+void launch_long_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv,
+                     const float* kmask, void* ctx, long long ldc, float* probs, int nseq, int lq, int lk, int nh, int hd,
+                     float scale, float p_drop, uint64_t seed, uint64_t off, hipStream_t st) {
+  set_attrs<T>();
+  hipLaunchKernelGGL((long_fwd_kernel<T, SAVE>), dim3(nseq * nh, (lq + QB - 1) / QB), dim3(NT), lds_q(lk, hd), st,
+                     (const T*)q, ldq, (const T*)k, ldk, (const T*)v, ldv, kmask, (T*)ctx, ldc, probs, lq, lk, nh, hd,
+                     scale, p_drop, seed, off);
 }
 
 }  // namespace
@@ -320,23 +333,17 @@ extern "C" int k3m_attn_long_fwd(const void* q, long long ldq, const void* k, lo
                                  long long ldv, const float* kmask, void* ctx, long long ldc, float* probs, int nseq,
                                  int lq, int lk, int nh, int hd, float scale, float p_drop, uint64_t seed, uint64_t off,
                                  int dtype, hipStream_t st) {
-  K3M_ARG(q && k && v && ctx && probs && nh > 0 && nseq >= 0);
+  K3M_ARG(q && k && v && ctx && nh > 0 && nseq >= 0);   // probs == NULL: the forward-only form
   K3M_ARG(lq > 0 && lk > 0 && lk <= MAXLK && hd > 0 && hd <= MAXD && hd % 32 == 0);
   K3M_ARG(dtype == K3M_F32 || dtype == K3M_BF16);
   K3M_ARG(vec_ok(q, ldq, dtype) && vec_ok(k, ldk, dtype) && vec_ok(v, ldv, dtype));
   if (nseq == 0) return 0;
-  const dim3 grid(nseq * nh, (lq + QB - 1) / QB);
-  const size_t lds = lds_q(lk, hd);
-  if (dtype == K3M_F32) {
-    set_attrs<float>();
-    hipLaunchKernelGGL(long_fwd_kernel<float>, grid, dim3(NT), lds, st, (const float*)q, ldq, (const float*)k, ldk,
-                       (const float*)v, ldv, kmask, (float*)ctx, ldc, probs, lq, lk, nh, hd, scale, p_drop, seed, off);
-  } else {
-    set_attrs<bf16_t>();
-    hipLaunchKernelGGL(long_fwd_kernel<bf16_t>, grid, dim3(NT), lds, st, (const bf16_t*)q, ldq, (const bf16_t*)k, ldk,
-                       (const bf16_t*)v, ldv, kmask, (bf16_t*)ctx, ldc, probs, lq, lk, nh, hd, scale, p_drop, seed,
-                       off);
-  }
+  if (dtype == K3M_F32)
+    probs ? launch_long_fwd<float, true>(q, ldq, k, ldk, v, ldv, kmask, ctx, ldc, probs, nseq, lq, lk, nh, hd, scale, p_drop, seed, off, st)
+          : launch_long_fwd<float, false>(q, ldq, k, ldk, v, ldv, kmask, ctx, ldc, probs, nseq, lq, lk, nh, hd, scale, p_drop, seed, off, st);
+  else
+    probs ? launch_long_fwd<bf16_t, true>(q, ldq, k, ldk, v, ldv, kmask, ctx, ldc, probs, nseq, lq, lk, nh, hd, scale, p_drop, seed, off, st)
+          : launch_long_fwd<bf16_t, false>(q, ldq, k, ldk, v, ldv, kmask, ctx, ldc, probs, nseq, lq, lk, nh, hd, scale, p_drop, seed, off, st);
   K3M_CHECK_LAUNCH();
   return 0;
 }

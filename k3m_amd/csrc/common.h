@@ -15,6 +15,12 @@
     if (!(cond)) return K3M_EINVAL;                          \
   } while (0)
 
+// Kernel-template value of the forward-only bias+GELU epilogue (K3mGemm.epilogue == K3M_EPI_BIAS_GELU with
+// aux == NULL): C = gelu(acc + bias) by the formulas of K3M_EPI_BIAS_GELU, with no store to aux in the kernel.
+// k3m_gemm / k3m_gemm_grouped choose it per launch on the host; it is not part of the public enum.
+#define K3M_EPI_BIAS_GELU_NS 5
+constexpr bool k3m_epi_gelu(int epi) { return epi == K3M_EPI_BIAS_GELU || epi == K3M_EPI_BIAS_GELU_NS; }
+
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 

@@ -47,6 +47,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
         can_old = false;
         break;
       }
+      case K3M_EPI_BIAS_GELU_NS: o = gelu_f(s + bias[col]); can_old = false; break;   // forward-only: no aux
       case K3M_EPI_DGELU: o = alpha * s * dgelu_f(aux[(long long)row * ldaux + col]); break;
       case K3M_EPI_BIAS_SIGMOID: o = sigmoid_f(s + bias[col]); can_old = false; break;
       default: o = alpha * s;
@@ -68,6 +69,7 @@ int launch_epi(const K3mGemm& g, hipStream_t st) {
     K3M_GEMM_CASE(K3M_EPI_NONE)
     K3M_GEMM_CASE(K3M_EPI_BIAS)
     K3M_GEMM_CASE(K3M_EPI_BIAS_GELU)
+    K3M_GEMM_CASE(K3M_EPI_BIAS_GELU_NS)
     K3M_GEMM_CASE(K3M_EPI_DGELU)
     K3M_GEMM_CASE(K3M_EPI_BIAS_SIGMOID)
 #undef K3M_GEMM_CASE
@@ -106,6 +108,7 @@ int launch_x6_epi(const K3mGemm& g, hipStream_t st) {
     K3M_GEMM_CASE(K3M_EPI_NONE)
     K3M_GEMM_CASE(K3M_EPI_BIAS)
     K3M_GEMM_CASE(K3M_EPI_BIAS_GELU)
+    K3M_GEMM_CASE(K3M_EPI_BIAS_GELU_NS)
     K3M_GEMM_CASE(K3M_EPI_DGELU)
     K3M_GEMM_CASE(K3M_EPI_BIAS_SIGMOID)
 #undef K3M_GEMM_CASE
@@ -200,6 +203,9 @@ extern "C" int k3m_gemm(const K3mGemm* gp, hipStream_t st) {
   const bool colsum = (gp->epilogue & K3M_GEMM_COLSUM_SLABS) != 0;
   K3mGemm gl = *gp;
   gl.epilogue &= ~(K3M_GEMM_SLABS_ONLY | K3M_GEMM_COLSUM_SLABS);
+  K3M_ARG(gl.epilogue != K3M_EPI_BIAS_GELU_NS);   // internal: chosen here, never passed in
+  // bias+GELU without a save buffer: the forward-only kernel instantiation (no store to aux)
+  if (gl.epilogue == K3M_EPI_BIAS_GELU && !gl.aux) gl.epilogue = K3M_EPI_BIAS_GELU_NS;
   // kernels read a non-split ws as the COLSUM_SLABS request
   if (!colsum && gl.splitk <= 1) gl.ws = nullptr;
   const K3mGemm& g = gl;
@@ -375,6 +381,7 @@ int launch_grouped_epi(const k3m_x6::GemmGroup& grp, int epi, hipStream_t st) {
     K3M_GROUP_CASE(K3M_EPI_NONE)
     K3M_GROUP_CASE(K3M_EPI_BIAS)
     K3M_GROUP_CASE(K3M_EPI_BIAS_GELU)
+    K3M_GROUP_CASE(K3M_EPI_BIAS_GELU_NS)
     K3M_GROUP_CASE(K3M_EPI_DGELU)
     K3M_GROUP_CASE(K3M_EPI_BIAS_SIGMOID)
 #undef K3M_GROUP_CASE
@@ -396,6 +403,8 @@ extern "C" int k3m_gemm_grouped(const K3mGemm* gs_in, int count, hipStream_t st)
     slabs_only[i] = (gs[i].epilogue & K3M_GEMM_SLABS_ONLY) != 0;
     colsum[i] = (gs[i].epilogue & K3M_GEMM_COLSUM_SLABS) != 0;
     gs[i].epilogue &= ~(K3M_GEMM_SLABS_ONLY | K3M_GEMM_COLSUM_SLABS);
+    K3M_ARG(gs[i].epilogue != K3M_EPI_BIAS_GELU_NS);
+    if (gs[i].epilogue == K3M_EPI_BIAS_GELU && !gs[i].aux) gs[i].epilogue = K3M_EPI_BIAS_GELU_NS;
     if (!colsum[i] && gs[i].splitk <= 1) gs[i].ws = nullptr;
     K3M_ARG(!slabs_only[i] || (gs[i].splitk > 1 && gs[i].ldc == gs[i].n));
     K3M_ARG(!colsum[i] || (gs[i].epilogue == K3M_EPI_DGELU && gs[i].splitk <= 1 && gs[i].beta == 0.f && gs[i].ws));
@@ -429,6 +438,7 @@ extern "C" int k3m_gemm_grouped(const K3mGemm* gs_in, int count, hipStream_t st)
   if (!same) {   // not one template: launch each on its own
     for (int i = 0; i < count; ++i) {
       K3mGemm gi = gs[i];
+      if (gi.epilogue == K3M_EPI_BIAS_GELU_NS) gi.epilogue = K3M_EPI_BIAS_GELU;   // k3m_gemm selects it again
       if (slabs_only[i]) gi.epilogue |= K3M_GEMM_SLABS_ONLY;
       if (colsum[i]) gi.epilogue |= K3M_GEMM_COLSUM_SLABS;
       const int rc = k3m_gemm(&gi, st);

@@ -557,7 +557,7 @@ __device__ __forceinline__ void epi_math8(const float (&v)[8], const float (&bb)
       o[e] = alpha * v[e];
     } else if constexpr (EPI == K3M_EPI_BIAS) {
       o[e] = alpha * (v[e] + bb[e]);
-    } else if constexpr (EPI == K3M_EPI_BIAS_GELU) {
+    } else if constexpr (k3m_epi_gelu(EPI)) {
       pa[e] = v[e] + bb[e];
       o[e] = gelu_fast(to_f(from_f<bf16_t>(pa[e])));  // gelu of the stored pre-activation the backward sees
     } else if constexpr (EPI == K3M_EPI_DGELU) {
@@ -603,7 +603,7 @@ __device__ __forceinline__ void epilogue(const K3mGemm& g, int m0, int n0, uint1
   CT* aux = static_cast<CT*>(g.aux);
   const float* bias = g.bias;
   constexpr bool HAS_AUX = EPI == K3M_EPI_BIAS_GELU || EPI == K3M_EPI_DGELU;
-  constexpr bool HAS_BIAS = EPI == K3M_EPI_BIAS || EPI == K3M_EPI_BIAS_GELU || EPI == K3M_EPI_BIAS_SIGMOID;
+  constexpr bool HAS_BIAS = EPI == K3M_EPI_BIAS || k3m_epi_gelu(EPI) || EPI == K3M_EPI_BIAS_SIGMOID;
   constexpr bool CAN_OLD = EPI == K3M_EPI_NONE || EPI == K3M_EPI_BIAS || EPI == K3M_EPI_DGELU;
   const bool cvec = (ldc % 8 == 0) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0) &&
                     (!HAS_AUX || ((g.ldaux % 8 == 0) && ((reinterpret_cast<uintptr_t>(aux) & 15) == 0)));

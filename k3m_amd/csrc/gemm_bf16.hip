@@ -308,7 +308,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_bf16_kernel(K3mGemm g) {
   CT* aux = static_cast<CT*>(g.aux);
   const float* bias = g.bias;
   constexpr bool HAS_AUX = EPI == K3M_EPI_BIAS_GELU || EPI == K3M_EPI_DGELU;
-  constexpr bool HAS_BIAS = EPI == K3M_EPI_BIAS || EPI == K3M_EPI_BIAS_GELU || EPI == K3M_EPI_BIAS_SIGMOID;
+  constexpr bool HAS_BIAS = EPI == K3M_EPI_BIAS || k3m_epi_gelu(EPI) || EPI == K3M_EPI_BIAS_SIGMOID;
   const bool cvec = (ldc % 8 == 0) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0) &&
                     (!HAS_AUX || ((g.ldaux % 8 == 0) && ((reinterpret_cast<uintptr_t>(aux) & 15) == 0)));
   const int lr = lane / LPR, lc = (lane % LPR) * 8;
@@ -356,7 +356,7 @@ __global__ __launch_bounds__(NT, 2) void gemm_bf16_kernel(K3mGemm g) {
           o[e] = alpha * v[e];
         } else if constexpr (EPI == K3M_EPI_BIAS) {
           o[e] = alpha * (v[e] + bb[e]);
-        } else if constexpr (EPI == K3M_EPI_BIAS_GELU) {
+        } else if constexpr (k3m_epi_gelu(EPI)) {
           pa[e] = v[e] + bb[e];
           o[e] = gelu_fast(to_f(from_f<CT>(pa[e])));  // gelu of the stored pre-activation the backward sees
         } else if constexpr (EPI == K3M_EPI_DGELU) {
@@ -407,6 +407,7 @@ int launch_epi(const K3mGemm& g, hipStream_t st) {
     K3M_GEMM_CASE(K3M_EPI_NONE)
     K3M_GEMM_CASE(K3M_EPI_BIAS)
     K3M_GEMM_CASE(K3M_EPI_BIAS_GELU)
+    K3M_GEMM_CASE(K3M_EPI_BIAS_GELU_NS)
     K3M_GEMM_CASE(K3M_EPI_DGELU)
     K3M_GEMM_CASE(K3M_EPI_BIAS_SIGMOID)
 #undef K3M_GEMM_CASE
@@ -493,7 +494,7 @@ const int kB16Dual = k3m_env_int("K3M_B16_DUAL", 2);
 // 256 x 128 tiles only unless bit 2 is set (the 256 x 256 ping-pong loop spills its fragment addresses)
 // measured slower on config 3 (profiles/r5d/README.txt): off
 const int kB16PP = k3m_env_int("K3M_B16_PP", 0);
-constexpr bool dual_epi(int epi) { return epi == K3M_EPI_BIAS_GELU || epi == K3M_EPI_DGELU; }
+constexpr bool dual_epi(int epi) { return k3m_epi_gelu(epi) || epi == K3M_EPI_DGELU; }
 // K3M_B16_WS: the K-contiguous forwards with a bf16 C on the epilogue-wave kernel (gemm_b16_ws.h): bit 0 the bias+GELU
 // epilogue, bit 1 bias / none.  Needs K % 32 == 0 and K >= 32 * ws::KMIN, beta = 0, no split-K, aligned C / aux / bias.
 const int kB16WS = k3m_env_int("K3M_B16_WS", 0);
@@ -596,6 +597,7 @@ int big_launch_epi_mf(const K3mGemm& g, hipStream_t st) {
     K3M_GEMM_CASE(K3M_EPI_NONE)
     K3M_GEMM_CASE(K3M_EPI_BIAS)
     K3M_GEMM_CASE(K3M_EPI_BIAS_GELU)
+    K3M_GEMM_CASE(K3M_EPI_BIAS_GELU_NS)
     K3M_GEMM_CASE(K3M_EPI_DGELU)
     K3M_GEMM_CASE(K3M_EPI_BIAS_SIGMOID)
 #undef K3M_GEMM_CASE
@@ -644,6 +646,7 @@ int big_grouped_epi_mf(const k3m_b16::GemmGroup& grp, int epi, hipStream_t st) {
     K3M_GROUP_CASE(K3M_EPI_NONE)
     K3M_GROUP_CASE(K3M_EPI_BIAS)
     K3M_GROUP_CASE(K3M_EPI_BIAS_GELU)
+    K3M_GROUP_CASE(K3M_EPI_BIAS_GELU_NS)
     K3M_GROUP_CASE(K3M_EPI_DGELU)
     K3M_GROUP_CASE(K3M_EPI_BIAS_SIGMOID)
 #undef K3M_GROUP_CASE

@@ -264,7 +264,7 @@ __device__ __forceinline__ void epi_math(const float (&v)[8], const float (&bb)[
       o[e] = alpha * v[e];
     } else if constexpr (EPI == K3M_EPI_BIAS) {
       o[e] = alpha * (v[e] + bb[e]);
-    } else if constexpr (EPI == K3M_EPI_BIAS_GELU) {
+    } else if constexpr (k3m_epi_gelu(EPI)) {   // (the forward-only form computes the same pa and keeps it)
       pa[e] = v[e] + bb[e];
       o[e] = gelu_f(pa[e]);
     } else if constexpr (EPI == K3M_EPI_DGELU) {
@@ -325,7 +325,7 @@ __device__ __forceinline__ void epilogue_r(const K3mGemm& g, int m0, int n0, flo
   float* aux = static_cast<float*>(g.aux);
   const float* bias = g.bias;
   constexpr bool HAS_AUX = EPI == K3M_EPI_BIAS_GELU || EPI == K3M_EPI_DGELU;
-  constexpr bool HAS_BIAS = EPI == K3M_EPI_BIAS || EPI == K3M_EPI_BIAS_GELU || EPI == K3M_EPI_BIAS_SIGMOID;
+  constexpr bool HAS_BIAS = EPI == K3M_EPI_BIAS || k3m_epi_gelu(EPI) || EPI == K3M_EPI_BIAS_SIGMOID;
   constexpr bool CAN_OLD = EPI == K3M_EPI_NONE || EPI == K3M_EPI_BIAS || EPI == K3M_EPI_DGELU;
   const bool cvec = (ldc % 4 == 0) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0) &&
                     (!HAS_AUX || ((g.ldaux % 4 == 0) && ((reinterpret_cast<uintptr_t>(aux) & 15) == 0)));

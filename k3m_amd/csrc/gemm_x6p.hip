@@ -619,6 +619,7 @@ int launch(const GemmGroup& grp, int epi, int nblk, hipStream_t st) {
     K3M_P_CASE(K3M_EPI_NONE)
     K3M_P_CASE(K3M_EPI_BIAS)
     K3M_P_CASE(K3M_EPI_BIAS_GELU)
+    K3M_P_CASE(K3M_EPI_BIAS_GELU_NS)
     K3M_P_CASE(K3M_EPI_DGELU)
     K3M_P_CASE(K3M_EPI_BIAS_SIGMOID)
 #undef K3M_P_CASE
@@ -680,6 +681,7 @@ int k3m_x6_persistent_launch(const k3m_x6::GemmGroup& grp, bool t256, bool ak, b
 int k3m_x6_variant_launch(const K3mGemm& g, int variant, hipStream_t st) {
   const bool ak = g.a_trans == 0, bk = g.b_trans == 1;
   if (variant < 1 || variant > 4 || !(ak && bk) || (variant >= 3 && g.epilogue == K3M_EPI_DGELU)) return -1;
+  if (g.epilogue == K3M_EPI_BIAS_GELU_NS) return -1;   // the lab tiles have no forward-only form: the product tiles run it
   if (variant >= 3 && g.epilogue != K3M_EPI_DGELU) {
     // one wave per SIMD: 256x256 tile over 2x2 waves of 128x128 (256 accumulators, up to 512 registers
     // per wave): twice the MFMAs per fragment read, no register aliasing between the staged global loads

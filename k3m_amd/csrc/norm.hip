@@ -45,8 +45,9 @@ __device__ __forceinline__ floatx4 round4(floatx4 v) {
 
 // ------------------------------------------------------------------ LayerNorm forward
 // NV = cols / 256 is a template parameter: with a runtime chunk count every load sat under a per-element
-// condition, which hipcc compiles to a branch with a vmcnt(0) inside (each load its own round trip)
-template <typename T, int NV>
+// condition, which hipcc compiles to a branch with a vmcnt(0) inside (each load its own round trip).
+// SAVE = false: the forward-only form (k3m_ln_fwd with xhat == rstd == NULL), no xhat / rstd store in the kernel
+template <typename T, int NV, bool SAVE = true>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res,
                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
                                                      T* __restrict__ y, T* __restrict__ xhat, float* __restrict__ rstd,
@@ -88,13 +89,17 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
     }
   const float var = wave_sum(sq) / cols;
   const float rs = 1.0f / sqrtf(var + eps);
-  if (lane == 0 && rstd) rstd[row] = rs;
+  if constexpr (SAVE) {
+    if (lane == 0 && rstd) rstd[row] = rs;
+  }
 #pragma unroll
   for (int j = 0; j < MAXV; ++j)
     if (j < nv) {
       const int c = (lane + 64 * j) * 4;
       const floatx4 xh = v[j] * rs;
-      if (xhat) st4<T>(xhat + base + c, xh);
+      if constexpr (SAVE) {
+        if (xhat) st4<T>(xhat + base + c, xh);
+      }
       const floatx4 g = *reinterpret_cast<const floatx4*>(gamma + c);
       const floatx4 b = *reinterpret_cast<const floatx4*>(beta + c);
       floatx4 o = g * xh + b;
@@ -343,7 +348,7 @@ __device__ __forceinline__ float half_sum(float v) {   // over the 32 lanes of a
   return v;
 }
 
-template <int NV>
+template <int NV, bool SAVE = true>
 __global__ __launch_bounds__(256) void ln_fwd_bf16_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ res,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
                                                           bf16_t* __restrict__ y, bf16_t* __restrict__ xhat,
@@ -390,7 +395,9 @@ __global__ __launch_bounds__(256) void ln_fwd_bf16_kernel(const bf16_t* __restri
     }
   const float var = half_sum(sq) / cols;
   const float rs = 1.0f / sqrtf(var + eps);
-  if (l == 0 && rstd) rstd[row] = rs;
+  if constexpr (SAVE) {
+    if (l == 0 && rstd) rstd[row] = rs;
+  }
 #pragma unroll
   for (int j = 0; j < MAXV8; ++j)
     if (j < nv) {
@@ -404,7 +411,9 @@ __global__ __launch_bounds__(256) void ln_fwd_bf16_kernel(const bf16_t* __restri
         o[e] = g[e] * xh[e] + b[e];
         if (p_out > 0.f) o[e] *= k3m_drop(dout, off_out + base + c + e);
       }
-      if (xhat) st8bf(xhat + base + c, xh);
+      if constexpr (SAVE) {
+        if (xhat) st8bf(xhat + base + c, xh);
+      }
       st8bf(y + base + c, o);
     }
 }
@@ -849,11 +858,12 @@ const int kLnVecBwdRows = k3m_env_int("K3M_LN_VEC_BWD_ROWS", 16384);
     return K3M_EINVAL;                    \
   }
 
-extern "C" int k3m_ln_fwd(const void* x, const void* res, const float* gamma, const float* beta, void* y, void* xhat,
-                          float* rstd, int rows, int cols, float eps, float p_in, float p_out, uint64_t seed,
-                          uint64_t off_in, uint64_t off_out, int dtype, hipStream_t st) {
-  K3M_ARG(x && gamma && beta && y && rows >= 0 && cols % 256 == 0 && cols <= 1024 && cols > 0);
-  if (rows == 0) return 0;
+namespace {
+// SAVE: the saving kernels, or the forward-only instantiations (no xhat / rstd store)
+template <bool SAVE>
+int launch_ln_fwd(const void* x, const void* res, const float* gamma, const float* beta, void* y, void* xhat,
+                  float* rstd, int rows, int cols, float eps, float p_in, float p_out, uint64_t seed, uint64_t off_in,
+                  uint64_t off_out, int dtype, hipStream_t st) {
   const int nv = cols >> 8;
 #define K3M_LN_NV(F)   \
   switch (nv) {        \
@@ -863,22 +873,35 @@ extern "C" int k3m_ln_fwd(const void* x, const void* res, const float* gamma, co
     default: F(4);       \
   }
   if (dtype == K3M_BF16 && kLnBf16Vec && rows >= LN_VEC_FWD_ROWS) {
-#define K3M_LNF16(NV_)                                                                                        \
-  hipLaunchKernelGGL(ln_fwd_bf16_kernel<NV_>, dim3(k3m_cdiv(rows, 8)), dim3(256), 0, st, (const bf16_t*)x,   \
-                      (const bf16_t*)res, gamma, beta, (bf16_t*)y, (bf16_t*)xhat, rstd, rows, cols, eps, p_in, \
+#define K3M_LNF16(NV_)                                                                                               \
+  hipLaunchKernelGGL((ln_fwd_bf16_kernel<NV_, SAVE>), dim3(k3m_cdiv(rows, 8)), dim3(256), 0, st, (const bf16_t*)x,  \
+                      (const bf16_t*)res, gamma, beta, (bf16_t*)y, (bf16_t*)xhat, rstd, rows, cols, eps, p_in,      \
                       p_out, seed, off_in, off_out)
     K3M_LN_NV(K3M_LNF16);
 #undef K3M_LNF16
   } else {
-#define K3M_LNF(NV_)                                                                                          \
-  hipLaunchKernelGGL((ln_fwd_kernel<T, NV_>), dim3(k3m_cdiv(rows, 4)), dim3(256), 0, st, (const T*)x,       \
-                      (const T*)res, gamma, beta, (T*)y, (T*)xhat, rstd, rows, cols, eps, p_in, p_out, seed,  \
+#define K3M_LNF(NV_)                                                                                                 \
+  hipLaunchKernelGGL((ln_fwd_kernel<T, NV_, SAVE>), dim3(k3m_cdiv(rows, 4)), dim3(256), 0, st, (const T*)x,         \
+                      (const T*)res, gamma, beta, (T*)y, (T*)xhat, rstd, rows, cols, eps, p_in, p_out, seed,        \
                       off_in, off_out)
     DISPATCH_T(dtype, K3M_LN_NV(K3M_LNF));
 #undef K3M_LNF
   }
   K3M_CHECK_LAUNCH();
   return 0;
+}
+}  // namespace
+
+extern "C" int k3m_ln_fwd(const void* x, const void* res, const float* gamma, const float* beta, void* y, void* xhat,
+                          float* rstd, int rows, int cols, float eps, float p_in, float p_out, uint64_t seed,
+                          uint64_t off_in, uint64_t off_out, int dtype, hipStream_t st) {
+  K3M_ARG(x && gamma && beta && y && rows >= 0 && cols % 256 == 0 && cols <= 1024 && cols > 0);
+  K3M_ARG((xhat == nullptr) == (rstd == nullptr));   // both saved, or the forward-only form
+  if (rows == 0) return 0;
+  return xhat ? launch_ln_fwd<true>(x, res, gamma, beta, y, xhat, rstd, rows, cols, eps, p_in, p_out, seed, off_in,
+                                    off_out, dtype, st)
+              : launch_ln_fwd<false>(x, res, gamma, beta, y, xhat, rstd, rows, cols, eps, p_in, p_out, seed, off_in,
+                                     off_out, dtype, st);
 }
 
 // at least kLnRowsPerSlab rows per slab (per workgroup): at 4, a short LayerNorm (2,304 rows) wrote 512 x 3

@@ -32,7 +32,7 @@ import torch
 from . import debug
 from . import _lib as L
 from . import ops
-from .params import dynamic_attention, flat_layout, frozen_names
+from .params import dynamic_attention, flat_layout, frozen_names, is_frozen
 
 EPS = 1e-12
 
@@ -154,11 +154,12 @@ class AddLN(object):
     def __init__(self, ln, p):
         self.ln, self.p = ln, p
 
-    def fwd(self, x, res, rng, out=None):
+    def fwd(self, x, res, rng, out=None, save=True):
+        """save=False: the forward-only kernel form (no xhat / rstd); the same draws, nothing for a backward"""
         M, H = x.shape
         y = out if out is not None else torch.empty_like(x)
-        xhat = torch.empty((M, H), dtype=x.dtype, device=x.device)
-        rstd = torch.empty((M,), dtype=torch.float32, device=x.device)
+        xhat = torch.empty((M, H), dtype=x.dtype, device=x.device) if save else None
+        rstd = torch.empty((M,), dtype=torch.float32, device=x.device) if save else None
         off = rng.take(M * H) if self.p > 0 else 0
         ops.ln_fwd(x, res, self.ln.g, self.ln.b, y, xhat, rstd, p_in=self.p, seed=rng.seed, off_in=off)
         return y, (xhat, rstd, rng.seed, off)
@@ -181,13 +182,14 @@ class FFN(object):
         self.o = Lin(fp, outp + ".dense")
         self.tail = AddLN(LN(fp, outp + ".LayerNorm"), p)
 
-    def fwd(self, h, rng, out=None):
+    def fwd(self, h, rng, out=None, save=True):
+        """save=False: no GELU pre-activation is written (the forward-only epilogue) and nothing is kept"""
         M = h.shape[0]
         I = self.i.W.shape[0]
-        u = torch.empty((M, I), dtype=h.dtype, device=h.device)
+        u = torch.empty((M, I), dtype=h.dtype, device=h.device) if save else None
         f = self.i.fwd(h, epi=L.EPI_BIAS_GELU, aux=u)
         o = self.o.fwd(f)
-        y, tsv = self.tail.fwd(o, h, rng, out=out)
+        y, tsv = self.tail.fwd(o, h, rng, out=out, save=save)
         return y, (h, u, f, tsv)
 
     def bwd(self, dy, saved, dh_out=None):
@@ -207,15 +209,16 @@ def _flash(q, hd, lq, lk):
     return q.dtype == torch.bfloat16 and (ops.flash_fits(lq, lk, hd) or ops.flash_long_fits(lq, lk, hd))
 
 
-def _attn_fwd(q, k, v, mask, nseq, lq, lk, nh, p, rng, out=None):
+def _attn_fwd(q, k, v, mask, nseq, lq, lk, nh, p, rng, out=None, save=True):
+    """save=False: the forward-only kernel forms (no LSE / probability store); the saved tuple then holds None"""
     hd = q.shape[1] // nh
     ctx = out if out is not None else torch.empty((nseq * lq, q.shape[1]), dtype=q.dtype, device=q.device)
     off = rng.take(nseq * nh * lq * lk) if p > 0 else 0
     if _flash(q, hd, lq, lk):
-        stat = torch.empty((nseq * nh * lq,), dtype=torch.float32, device=q.device)   # row LSE
+        stat = torch.empty((nseq * nh * lq,), dtype=torch.float32, device=q.device) if save else None   # row LSE
         ops.flash_attn_fwd(q, k, v, mask, ctx, stat, nseq, lq, lk, nh, hd, 1.0 / math.sqrt(hd), p, rng.seed, off)
-    else:
-        stat = torch.empty((nseq * nh * lq * lk,), dtype=torch.float32, device=q.device)   # probabilities
+    else:   # probabilities
+        stat = torch.empty((nseq * nh * lq * lk,), dtype=torch.float32, device=q.device) if save else None
         ops.attn_fwd(q, k, v, mask, ctx, stat, nseq, lq, lk, nh, hd, 1.0 / math.sqrt(hd), p, rng.seed, off)
     return ctx, (stat, mask, nseq, lq, lk, nh, hd, p, rng.seed, off)
 
@@ -314,6 +317,24 @@ class BertLayerOp(object):
         h1, tsv = self.tail.fwd(a, x, rng)
         y, fsv = self.ffn.fwd(h1, rng)
         return y, (x, qkv, ctx, asv, tsv, fsv, segs, dsv)
+
+    def fwd_only(self, x, segs, rng, save=False):
+        """A layer below the fixed_t_layer cut: the values and the rng.take sequence of fwd(), no saved state.
+        save=False runs the forward-only kernel forms (no GELU pre-activation, xhat / rstd, probabilities / LSE);
+        save=True (K3M_FROZEN_NOSAVE=0) the saving kernels into buffers dropped on return."""
+        assert self.dyn is None
+        M, H = x.shape
+        qkv = self.qkv.fwd(x)
+        ctx = torch.empty((M, H), dtype=x.dtype, device=x.device)
+        with ops.branches():
+            for (r0, nseq, ln, mask) in segs:
+                r1 = r0 + nseq * ln
+                ops.branch(_attn_fwd, qkv[r0:r1, 0:H], qkv[r0:r1, H:2 * H], qkv[r0:r1, 2 * H:], mask, nseq, ln, ln,
+                           self.nh, self.p_attn, rng, out=ctx[r0:r1], save=save)
+        a = self.o.fwd(ctx)
+        h1, _ = self.tail.fwd(a, x, rng, save=save)
+        y, _ = self.ffn.fwd(h1, rng, save=save)
+        return y
 
     def bwd(self, dy, saved, dyn_out=None):
         x, qkv, ctx, asv, tsv, fsv, segs, dsv = saved
@@ -550,6 +571,13 @@ def _ext_mask(m):
     return ((1.0 - m.to(torch.float32)) * -10000.0).contiguous()
 
 
+def _without_cut(cfg):
+    import copy
+    c = copy.copy(cfg)
+    c.fixed_t_layer = 0
+    return c
+
+
 def validate_config(cfg):
     """Configurations the engine refuses, checked before any device work.  Without the image modality
     (use_image false) the reference defines only the hard gate: its fusion modes 0, 2 and 3 add the absent
@@ -560,6 +588,13 @@ def validate_config(cfg):
                          % getattr(cfg, "if_pre_sampling", 1))
     # masked-region objective: 0 = KL against the detector's class probabilities, 1 = MSE regression of the
     # region's own feature (vilbert_k3m.py:2232-2237, :2745-2752)
+    ft, fv = int(getattr(cfg, "fixed_t_layer", 0)), int(getattr(cfg, "fixed_v_layer", 0))
+    if not 0 <= ft <= cfg.t_biattention_id[0]:
+        raise ValueError("fixed_t_layer=%d: the reference asserts fixed_t_layer <= t_biattention_id[0] = %d in every "
+                         "pair pass (vilbert_k3m.py:1185, :1363, :1539-1540)" % (ft, cfg.t_biattention_id[0]))
+    if fv != 0:
+        raise ValueError("fixed_v_layer=%d: no driver of the reference sets it (train_concap_struc.py:206-207, "
+                         "pretrain.py:1358-1359 and finetune.py:1318-1319 set fixed_t_layer only); not built" % fv)
     vt = getattr(cfg, "visual_target", 0)
     if vt == 2:
         raise ValueError("visual_target=2 (NCE) is not built: the reference's own forward fails for it, reading "
@@ -596,7 +631,13 @@ class K3MEngine(object):
         # (out["mlm_logits"] rows in compaction order — text rows, then PV rows, row-major; out["img_logits"])
         self.capture_logits = False
         c = cfg
-        assert getattr(c, "fixed_t_layer", 0) == 0 and getattr(c, "fixed_v_layer", 0) == 0
+        # text layers 0 .. fixed_t - 1 run forward-only (the reference's no_grad loop, vilbert_k3m.py:1188-1193):
+        # nothing of them is kept and the text stream's backward stops at the cut.  K3M_FROZEN_NOSAVE=0 keeps the
+        # saving kernels for them (A/B knob: the cost of the saves alone)
+        self.fixed_t = int(getattr(c, "fixed_t_layer", 0))
+        self.frozen_nosave = os.environ.get("K3M_FROZEN_NOSAVE", "1") != "0"
+        # the tensors that are never-grad because of the cut alone (the module surface leaves their .grad None)
+        self.cut_frozen = fp.frozen - {n for n, _ in fp.spec if is_frozen(n, _without_cut(c))} if self.fixed_t else set()
         assert not getattr(c, "in_batch_pairs", False) and not getattr(c, "fast_mode", False)
         assert getattr(c, "model", "bert") in ("bert", "roberta")
         assert c.with_coattention
@@ -672,6 +713,9 @@ class K3MEngine(object):
         sch += [("v", k) for k in range(v0, c.v_num_hidden_layers)]
         sch += [("t", k) for k in range(t0, c.num_hidden_layers)]
         return sch
+
+    def _below_cut(self, kind, i):
+        return kind == "t" and i < self.fixed_t
 
     # ------------------------------------------------------------ forward
     def _verify_hint(self, hint, cnt):
@@ -794,7 +838,8 @@ class K3MEngine(object):
         while si < len(sched):
             kind, i = sched[si]
             nxt = sched[si + 1] if si + 1 < len(sched) else None
-            if GROUP_TV and nxt is not None and {kind, nxt[0]} == {"t", "v"} and not (self.dyn_attn and kind == "t"):
+            if (GROUP_TV and nxt is not None and {kind, nxt[0]} == {"t", "v"} and not (self.dyn_attn and kind == "t")
+                    and not self._below_cut(kind, i) and not self._below_cut(*nxt)):
                 # a text layer and an image layer at the same schedule position are independent:
                 # run them in lock step so their GEMM stages share grouped launches.  With dynamic attention the
                 # image layer reads the text stream: independent only where the image layer comes first (after the
@@ -826,6 +871,9 @@ class K3MEngine(object):
                 op = self.text[i]
                 if not train:
                     op = _eval_view(op)
+                if i < self.fixed_t:   # below the cut: forward-only, nothing kept
+                    XT = op.fwd_only(XT, tsegs, rng, save=not self.frozen_nosave)
+                    continue
                 XT, sv = op.fwd(XT, tsegs, rng)
                 enc.append((kind, i, sv))
             elif kind == "v":
@@ -1338,8 +1386,11 @@ class K3MEngine(object):
                 op = self.image[i] if ctx["train"] else _eval_view(self.image[i])
                 pool_grads = []
                 dXV = op.bwd(dXV, sv, dyn_out=pool_grads)
-                for pg in pool_grads:   # before any earlier text op consumes these rows of dXT
-                    pg.add_into(dparts(dXT))
+                # below a cut with no text layer left to run backward the partner was computed without a graph: the
+                # pool gradient is dropped (dXT ends at the cut)
+                if self.fixed_t == 0 or any(k_ == "t" for k_, _, _ in renc[ei:]):
+                    for pg in pool_grads:   # before any earlier text op consumes these rows of dXT
+                        pg.add_into(dparts(dXT))
             else:
                 s_tv, s_pv, s_tt, ops_ = sv
                 dXT2 = torch.empty_like(dXT)
@@ -1359,11 +1410,14 @@ class K3MEngine(object):
         # ---- embeddings
         ph = self.p_h if ctx["train"] else 0.0
         dt_ = d_ind["t"]
-        ops.convert(dXT[0:BT], dt_, accumulate=True)
-        ops.convert(dXT[BT:2 * BT], dt_, accumulate=True)
         dp_ = d_ind["pv"]
-        ops.convert(dXT[2 * BT:2 * BT + BP], dp_, accumulate=True)
-        ops.convert(dXT[2 * BT + BP:], dp_, accumulate=True)
+        if self.fixed_t == 0:
+            ops.convert(dXT[0:BT], dt_, accumulate=True)
+            ops.convert(dXT[BT:2 * BT], dt_, accumulate=True)
+            ops.convert(dXT[2 * BT:2 * BT + BP], dp_, accumulate=True)
+            ops.convert(dXT[2 * BT + BP:], dp_, accumulate=True)
+        # else: dXT is the gradient at the cut; the layers below ran without a graph, so it ends here and the
+        # text embeddings get the gradient of their direct consumer (the fusion's individual candidate) alone
         dv_ = d_ind["v"]
         ops.convert(dXV[0:BR], dv_, accumulate=True)
         ops.convert(dXV[BR:], dv_, accumulate=True)
@@ -1371,8 +1425,11 @@ class K3MEngine(object):
         gword = fp.g["embeddings.word_embeddings.weight"]
         gpos = fp.g["embeddings.position_embeddings.weight"]
         gtyp = fp.g["embeddings.token_type_embeddings.weight"]
-        for dy, xh, rs, off, ids, tt in ((dt_, xh_t, rs_t, off_t, batch["input_ids"], batch["segment_ids"]),
-                                         (dp_, xh_p, rs_p, off_p, batch["input_ids_pv"], batch["segment_ids_pv"])):
+        # interactive-only fusion has no individual candidate: below a cut nothing reaches the text embeddings
+        text_emb = () if (self.fixed_t and mode == 3) else (
+            (dt_, xh_t, rs_t, off_t, batch["input_ids"], batch["segment_ids"]),
+            (dp_, xh_p, rs_p, off_p, batch["input_ids_pv"], batch["segment_ids_pv"]))
+        for dy, xh, rs, off, ids, tt in text_emb:
             ds = torch.empty_like(dy)
             ops.ln_bwd(dy, xh, rs, self.emb_ln.g, ds, ds, self.emb_ln.gg, self.emb_ln.gb, p_out=ph,
                        seed=ctx["seed"], off_out=off)

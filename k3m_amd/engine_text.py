@@ -67,7 +67,9 @@ def forward(eng, batch, train=True, noise=None, ent_neg=None, val_neg=None, seed
     tsegs = [(0, B, T, mask_t), (BT, B, P, mask_p)]
     enc = []
     for kind, i in eng.schedule:
-        if kind == "t":
+        if kind == "t" and i < eng.fixed_t:   # below the fixed_t_layer cut: forward-only, nothing kept
+            XT = view(eng.text[i]).fwd_only(XT, tsegs, rng, save=not eng.frozen_nosave)
+        elif kind == "t":
             XT, sv = view(eng.text[i]).fwd(XT, tsegs, rng)
             enc.append((kind, i, sv))
         else:   # stream 1 = PV, stream 2 = title (BertConnectionLayer_two_text)
@@ -345,7 +347,8 @@ def backward(eng, ctx, w_mlm=1.0, w_lpm=1.0, grad_ready=None, w_mlm_pv=None):
 
     # ---- embeddings
     ph = eng.p_h if ctx["train"] else 0.0
-    ops.convert(dXT, d_ind, accumulate=True)
+    if eng.fixed_t == 0:   # (below a cut dXT ends at the cut: the embeddings keep the individual candidate's gradient)
+        ops.convert(dXT, d_ind, accumulate=True)
     xh, rs, off_t, off_p = ctx["emb"]
     gword = fp.g["embeddings.word_embeddings.weight"]
     gpos = fp.g["embeddings.position_embeddings.weight"]

@@ -180,7 +180,8 @@ def gemm(a, a_trans, b, b_trans, c, m, n, k, epi=L.EPI_NONE, bias=None, aux=None
 
 
 def linear(x, W, b=None, out=None, epi=None, aux=None, alpha=1.0, beta=0.0, out_dtype=None):
-    """out = x . W^T (+ b) with epilogue; x [M,K] (row view), W [N,K]."""
+    """out = x . W^T (+ b) with epilogue; x [M,K] (row view), W [N,K].  epi EPI_BIAS_GELU with aux None: the
+    forward-only epilogue (no pre-activation store; out bit-identical)."""
     M, K = x.shape
     N = W.shape[0]
     if out is None:
@@ -468,6 +469,7 @@ def colsum(x, out, accumulate=True, alpha=1.0):
 
 # ------------------------------------------------------------------ LayerNorm / embeddings
 def ln_fwd(x, res, gamma, beta, y, xhat, rstd, p_in=0.0, p_out=0.0, seed=0, off_in=0, off_out=0, eps=1e-12):
+    """xhat = rstd = None: the forward-only kernel form (nothing saved for a backward; y bit-identical)."""
     rows, cols = x.shape
     for t in (x, res, y, xhat):
         assert t is None or (t.is_contiguous() or t.stride(0) == cols)
@@ -588,6 +590,7 @@ def flash_long_fits(lq, lk, hd):
 
 
 def attn_fwd(q, k, v, kmask, ctx, probs, nseq, lq, lk, nh, hd, scale, p_drop, seed, off):
+    """probs None: the forward-only kernel forms (no [nseq, nh, lq, lk] probability store; ctx bit-identical)."""
     name = "k3m_attn_fwd" if _short_fits(lq, lk, hd, False) else "k3m_attn_long_fwd"
     call(name, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kmask), ptr(ctx), _ld(ctx), ptr(probs),
          nseq, lq, lk, nh, hd, scale, p_drop, seed, off, dt(ctx), stream())
@@ -607,7 +610,8 @@ def attn_bwd(dctx, o, q, k, v, probs, dq, dk, dv, nseq, lq, lk, nh, hd, scale, p
 
 def flash_attn_fwd(q, k, v, kmask, ctx, lse, nseq, lq, lk, nh, hd, scale, p_drop, seed, off):
     """bf16 attention forward saving the row log-sum-exp (lse: fp32 [nseq*nh*lq]): the whole-head kernels of
-    attention_bf16.hip where they fit (L <= 128), else attention_flash_long.hip (L <= 512)."""
+    attention_bf16.hip where they fit (L <= 128), else attention_flash_long.hip (L <= 512).  lse None: the
+    forward-only kernel forms (no LSE store; ctx bit-identical)."""
     name = "k3m_flash_attn_fwd" if flash_fits(lq, lk, hd) else "k3m_flash_attn_long_fwd"
     call(name, ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(kmask), ptr(ctx), _ld(ctx),
          ptr(lse), nseq, lq, lk, nh, hd, scale, p_drop, seed, off, stream())

@@ -199,6 +199,8 @@ _FROZEN_RE = re.compile(r"(\.q_dense[12]\.|^t_pooler\.|^v_pooler\.|^cls\.seq_rel
 _SOFT_RE = re.compile(r"^soft_(v|t|pv)\.")
 _SCORE_RE = re.compile(r"^score_(self|cross1|cross2)_(v|t|pv)\.")
 _CROSS1_RE = re.compile(r"^score_cross1_(t|pv)\.")
+_TEXT_LAYER_RE = re.compile(r"^encoder\.layer\.(\d+)\.")
+WORD_EMB = "embeddings.word_embeddings.weight"
 
 
 def is_frozen(name, cfg=None):
@@ -214,8 +216,22 @@ def is_frozen(name, cfg=None):
 
     Without the image modality (``cfg.use_image`` false) the cross-1 partner of the text and PV streams is
     the absent image, so ``score_cross1_(t|pv)`` never enter the two-candidate gate (:2331-2374 with
-    ``sequence_c1 = None``): 36 never-grad tensors in the pretraining model, 34 in item alignment."""
+    ``sequence_c1 = None``): 36 never-grad tensors in the pretraining model, 34 in item alignment.
+
+    Frozen lower text layers (``cfg.fixed_t_layer`` = k > 0; BertEncoder runs ``encoder.layer.0 .. k-1`` under
+    no_grad, vilbert_k3m.py:1188-1193): their 16 k tensors join the set.  The embeddings keep the gradient of
+    their direct consumer, the fusion's individual candidate, so they stay trainable, except with interactive-only
+    fusion (3), which has no such candidate: there the text embeddings are never-grad too, but for the word
+    embeddings of the pretraining model (the tied MLM decoder).  Recorded from the reference for each case in
+    tests/golden/none_grad_fixed_t_layer.json."""
     mode = getattr(cfg, "if_pre_sampling", 1) if cfg is not None else 1
+    ft = int(getattr(cfg, "fixed_t_layer", 0)) if cfg is not None else 0
+    if ft > 0:
+        m = _TEXT_LAYER_RE.match(name)
+        if m and int(m.group(1)) < ft:
+            return True
+        if mode == 3 and name.startswith("embeddings."):
+            return not (name == WORD_EMB and getattr(cfg, "task", "pretrain") == "pretrain")
     if cfg is not None and not getattr(cfg, "use_image", True) and _CROSS1_RE.search(name):
         return True
     if mode == 2 and _SOFT_RE.search(name):

@@ -146,8 +146,12 @@ class BertForMultiModalPreTraining_tri_stru(nn.Module):
             self.engine.fp.grad.zero_()   # zero_grad(set_to_none=True) happened
 
     def _expose_grads(self):
+        cut = self.engine.cut_frozen   # below a fixed_t_layer cut: no gradient, as under the reference's no_grad
         for n in self._names:
             p = getattr(self, n.replace(".", "__"))
+            if n in cut:
+                p.grad = None
+                continue
             if p.grad is None or p.grad.data_ptr() != self.engine.fp.g[n].data_ptr():
                 p.grad = self.engine.fp.g[n]
 

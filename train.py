@@ -168,12 +168,10 @@ def main(argv=None):
     if "roberta" in args.model_name:
         config.model = "roberta"
     if args.freeze > config.t_biattention_id[0]:
-        # the reference then sets config.fixed_t_layer = t_biattention_id[0] (:206-207): the text layers below the
-        # first co-attention run under no_grad, which also cuts the embeddings' gradient.  The wide engine does not
-        # implement that truncated backward; refuse instead of training a different model.
-        raise SystemExit("--freeze %d > t_biattention_id[0] = %d (fixed_t_layer) is not supported by the MI355X "
-                         "engine; use --freeze <= %d" % (args.freeze, config.t_biattention_id[0],
-                                                         config.t_biattention_id[0]))
+        # as the reference (:206-207): the text layers below the first co-attention block run under no_grad.  That
+        # cuts the gradient that flowed down through them; the embeddings keep the gradient of their direct
+        # consumers (the fusion's individual candidate, the tied MLM decoder)
+        config.fixed_t_layer = config.t_biattention_id[0]
     config.with_coattention = args.with_coattention
     config.dynamic_attention = args.dynamic_attention
     config.if_pre_sampling = args.if_pre_sampling
