@@ -175,32 +175,13 @@ class AddLN(object):
 
 
 class FFN(object):
-    """BertIntermediate(gelu) + BertOutput (post-LN), vilbert_k3m.py:504-532 / :665-693."""
+    """BertIntermediate(gelu) + BertOutput (post-LN), vilbert_k3m.py:504-532 / :665-693: the parameters; the two
+    GEMM stages are issued by the owning op's step form."""
 
     def __init__(self, fp, inter, outp, p):
         self.i = Lin(fp, inter + ".dense")
         self.o = Lin(fp, outp + ".dense")
         self.tail = AddLN(LN(fp, outp + ".LayerNorm"), p)
-
-    def fwd(self, h, rng, out=None, save=True):
-        """save=False: no GELU pre-activation is written (the forward-only epilogue) and nothing is kept"""
-        M = h.shape[0]
-        I = self.i.W.shape[0]
-        u = torch.empty((M, I), dtype=h.dtype, device=h.device) if save else None
-        f = self.i.fwd(h, epi=L.EPI_BIAS_GELU, aux=u)
-        o = self.o.fwd(f)
-        y, tsv = self.tail.fwd(o, h, rng, out=out, save=save)
-        return y, (h, u, f, tsv)
-
-    def bwd(self, dy, saved, dh_out=None):
-        h, u, f, tsv = saved
-        dh = dh_out if dh_out is not None else torch.empty_like(h)
-        do = self.tail.bwd(dy, tsv, dh, dxsum=self.o.gb)
-        self.o.wgrad(do, f, bias_done=True)
-        du = self.o.dgrad(do, dgelu_aux=u, colsum_out=self.i.gb)   # + intermediate bias gradient
-        self.i.wgrad(du, h, bias_done=True)
-        self.i.dgrad(du, dx=dh, beta=1.0)
-        return dh
 
 
 def _flash(q, hd, lq, lk):
@@ -298,67 +279,14 @@ class BertLayerOp(object):
         self.ffn = FFN(fp, prefix + ".intermediate", prefix + ".output", p_hidden)
         self.nh, self.p_attn = nh, p_attn
 
-    def fwd(self, x, segs, rng, partner=None):
-        M, H = x.shape
-        qkv = self.qkv.fwd(x)
-        dsv = None
-        if self.dyn is not None:
-            dsv = self.dyn.gate(partner)
-            self.dyn.scale(qkv, dsv)
-        ctx = torch.empty((M, H), dtype=x.dtype, device=x.device)
-        asv = []
-        with ops.branches():   # the sequence segments (text 36, PV 128) are independent launches
-            for (r0, nseq, ln, mask) in segs:
-                r1 = r0 + nseq * ln
-                _, s = ops.branch(_attn_fwd, qkv[r0:r1, 0:H], qkv[r0:r1, H:2 * H], qkv[r0:r1, 2 * H:], mask, nseq, ln,
-                                  ln, self.nh, self.p_attn, rng, out=ctx[r0:r1])
-                asv.append(s)
-        a = self.o.fwd(ctx)
-        h1, tsv = self.tail.fwd(a, x, rng)
-        y, fsv = self.ffn.fwd(h1, rng)
-        return y, (x, qkv, ctx, asv, tsv, fsv, segs, dsv)
-
-    def fwd_only(self, x, segs, rng, save=False):
-        """A layer below the fixed_t_layer cut: the values and the rng.take sequence of fwd(), no saved state.
-        save=False runs the forward-only kernel forms (no GELU pre-activation, xhat / rstd, probabilities / LSE);
-        save=True (K3M_FROZEN_NOSAVE=0) the saving kernels into buffers dropped on return."""
-        assert self.dyn is None
-        M, H = x.shape
-        qkv = self.qkv.fwd(x)
-        ctx = torch.empty((M, H), dtype=x.dtype, device=x.device)
-        with ops.branches():
-            for (r0, nseq, ln, mask) in segs:
-                r1 = r0 + nseq * ln
-                ops.branch(_attn_fwd, qkv[r0:r1, 0:H], qkv[r0:r1, H:2 * H], qkv[r0:r1, 2 * H:], mask, nseq, ln, ln,
-                           self.nh, self.p_attn, rng, out=ctx[r0:r1], save=save)
-        a = self.o.fwd(ctx)
-        h1, _ = self.tail.fwd(a, x, rng, save=save)
-        y, _ = self.ffn.fwd(h1, rng, save=save)
-        return y
-
-    def bwd(self, dy, saved, dyn_out=None):
-        x, qkv, ctx, asv, tsv, fsv, segs, dsv = saved
-        M, H = x.shape
-        dh1 = self.ffn.bwd(dy, fsv)
-        dx = torch.empty_like(x)
-        da = self.tail.bwd(dh1, tsv, dx, dxsum=self.o.gb)
-        self.o.wgrad(da, ctx, bias_done=True)
-        dctx = self.o.dgrad(da)
-        dqkv = torch.empty_like(qkv)
-        with ops.branches():
-            for (r0, nseq, ln, mask), s in zip(segs, asv):
-                r1 = r0 + nseq * ln
-                ops.branch(_attn_bwd, dctx[r0:r1], ctx[r0:r1], qkv[r0:r1, 0:H], qkv[r0:r1, H:2 * H], qkv[r0:r1, 2 * H:],
-                           s, dqkv[r0:r1, 0:H], dqkv[r0:r1, H:2 * H], dqkv[r0:r1, 2 * H:])
-        if dsv is not None:
-            dyn_out.append(self.dyn.bwd(dqkv, qkv, dsv))
-        self.qkv.wgrad(dqkv, x)
-        self.qkv.dgrad(dqkv, dx=dx, beta=1.0)
-        return dx
-
-
-    # lock-step form (see ConnectionOp.fwd_steps): segments end at the GEMM stages
-    def fwd_steps(self, x, segs, rng, res, partner=None):
+    # One body per direction, cut into segments at the GEMM stages (generators): _run drives a lone layer, each
+    # GEMM launched at once; _lockstep drives independent layers together, one grouped launch per stage.  Inside
+    # a segment no op reads a GEMM output of the same segment.
+    def fwd_steps(self, x, segs, rng, partner=None, save=True):
+        """-> (y, saved).  save=False (a layer below the fixed_t_layer cut): the same values and rng.take sequence
+        from the forward-only kernel forms (no GELU pre-activation, xhat / rstd, probabilities / LSE); the saved
+        tuple then holds None in their places."""
+        assert save or self.dyn is None
         M, H = x.shape
         qkv = self.qkv.fwd(x)
         dsv = self.dyn.gate(partner) if self.dyn is not None else None
@@ -367,28 +295,32 @@ class BertLayerOp(object):
             self.dyn.scale(qkv, dsv)
         ctx = torch.empty((M, H), dtype=x.dtype, device=x.device)
         asv = []
-        for (r0, nseq, ln, mask) in segs:
-            r1 = r0 + nseq * ln
-            _, sv = _attn_fwd(qkv[r0:r1, 0:H], qkv[r0:r1, H:2 * H], qkv[r0:r1, 2 * H:], mask, nseq, ln, ln, self.nh,
-                              self.p_attn, rng, out=ctx[r0:r1])
-            asv.append(sv)
+        # the sequence segments (text 36, PV 128) are independent launches.  A region of its own: a branch waits
+        # only on what was issued before its region opened, and the scale above is in this segment
+        with ops.branches():
+            for (r0, nseq, ln, mask) in segs:
+                r1 = r0 + nseq * ln
+                _, sv = ops.branch(_attn_fwd, qkv[r0:r1, 0:H], qkv[r0:r1, H:2 * H], qkv[r0:r1, 2 * H:], mask, nseq, ln,
+                                   ln, self.nh, self.p_attn, rng, out=ctx[r0:r1], save=save)
+                asv.append(sv)
         a = self.o.fwd(ctx)
         yield
-        h1, tsv = self.tail.fwd(a, x, rng)
-        u = torch.empty((M, self.ffn.i.W.shape[0]), dtype=h1.dtype, device=h1.device)
+        h1, tsv = self.tail.fwd(a, x, rng, save=save)
+        u = torch.empty((M, self.ffn.i.W.shape[0]), dtype=h1.dtype, device=h1.device) if save else None
         f = self.ffn.i.fwd(h1, epi=L.EPI_BIAS_GELU, aux=u)
         yield
         o = self.ffn.o.fwd(f)
         yield
-        y, ts2 = self.ffn.tail.fwd(o, h1, rng)
-        res.append((y, (x, qkv, ctx, asv, tsv, (h1, u, f, ts2), segs, dsv)))
+        y, ts2 = self.ffn.tail.fwd(o, h1, rng, save=save)
+        return y, (x, qkv, ctx, asv, tsv, (h1, u, f, ts2), segs, dsv)
 
-    def bwd_steps(self, dy, saved, res, exact=False, dyn_out=None):
-        """res: [dx].  dyn_out: as in bwd(), receives a layer with dynamic attention's PoolGrad (the GEMM that
-        writes it is pending until the lock step's last flush).  exact: keep the bits of bwd().  One product differs otherwise: the
-        dGELU input gradient leaves the bias gradient's column sums as 32-row slabs from its epilogue, and a grouped
-        launch sums a slab's rows in the order of the tile the whole group runs on, so intermediate.dense.bias
-        moves in its last bit; that GEMM is then launched on its own, as bwd() launches it."""
+    def bwd_steps(self, dy, saved, exact=False, dyn_out=None):
+        """-> dx.  dyn_out: a list that receives a layer with dynamic attention's PoolGrad (under _lockstep the GEMM
+        that writes it is pending until the lock step's last flush).  exact: keep, inside a group, the bits of the
+        layer run on its own.  One product differs otherwise: the dGELU input gradient leaves the bias gradient's
+        column sums as 32-row slabs from its epilogue, and a grouped launch sums a slab's rows in the order of the
+        tile the whole group runs on, so intermediate.dense.bias moves in its last bit; that GEMM is then launched
+        on its own.  Outside a group exact changes nothing."""
         x, qkv, ctx, asv, tsv, fsv, segs, dsv = saved
         M, H = x.shape
         h1, u, f, ts2 = fsv
@@ -396,7 +328,7 @@ class BertLayerOp(object):
         do = self.ffn.tail.bwd(dy, ts2, dh1, dxsum=self.ffn.o.gb)
         self.ffn.o.wgrad(do, f, bias_done=True)
         with (ops.ungrouped() if exact else contextlib.nullcontext()):
-            du = self.ffn.o.dgrad(do, dgelu_aux=u, colsum_out=self.ffn.i.gb)
+            du = self.ffn.o.dgrad(do, dgelu_aux=u, colsum_out=self.ffn.i.gb)   # + intermediate bias gradient
         yield
         self.ffn.i.wgrad(du, h1, bias_done=True)
         self.ffn.i.dgrad(du, dx=dh1, beta=1.0)
@@ -407,15 +339,16 @@ class BertLayerOp(object):
         dctx = self.o.dgrad(da)
         yield
         dqkv = torch.empty_like(qkv)
-        for (r0, nseq, ln, mask), sv in zip(segs, asv):
-            r1 = r0 + nseq * ln
-            _attn_bwd(dctx[r0:r1], ctx[r0:r1], qkv[r0:r1, 0:H], qkv[r0:r1, H:2 * H], qkv[r0:r1, 2 * H:], sv,
-                      dqkv[r0:r1, 0:H], dqkv[r0:r1, H:2 * H], dqkv[r0:r1, 2 * H:])
+        with ops.branches():
+            for (r0, nseq, ln, mask), sv in zip(segs, asv):
+                r1 = r0 + nseq * ln
+                ops.branch(_attn_bwd, dctx[r0:r1], ctx[r0:r1], qkv[r0:r1, 0:H], qkv[r0:r1, H:2 * H], qkv[r0:r1, 2 * H:],
+                           sv, dqkv[r0:r1, 0:H], dqkv[r0:r1, H:2 * H], dqkv[r0:r1, 2 * H:])
         if dsv is not None:
             dyn_out.append(self.dyn.bwd(dqkv, qkv, dsv))
         self.qkv.wgrad(dqkv, x)
         self.qkv.dgrad(dqkv, dx=dx, beta=1.0)
-        res.append(dx)
+        return dx
 
 
 class ConnectionOp(object):
@@ -434,50 +367,15 @@ class ConnectionOp(object):
         self.f2 = FFN(fp, prefix + ".t_intermediate", prefix + ".t_output", p_ffn2)
         self.nh, self.pa1, self.pa2 = nh, p_attn1, p_attn2
 
-    def fwd(self, s1, s2, nseq, l1, l2, mask1, mask2, rng, out1, out2):
-        Hb = self.qkv1.W.shape[0] // 3
-        q1 = self.qkv1.fwd(s1)
-        q2 = self.qkv2.fwd(s2)
-        # ctx1: stream-2 queries over stream-1 keys (+ stream-1 mask); ctx2 the converse (:786-824)
-        ctx1, a1s = _attn_fwd(q2[:, 0:Hb], q1[:, Hb:2 * Hb], q1[:, 2 * Hb:], mask1, nseq, l2, l1, self.nh, self.pa1, rng)
-        ctx2, a2s = _attn_fwd(q1[:, 0:Hb], q2[:, Hb:2 * Hb], q2[:, 2 * Hb:], mask2, nseq, l1, l2, self.nh, self.pa2, rng)
-        h1, t1s = self.t1.fwd(self.d1.fwd(ctx2), s1, rng)
-        h2, t2s = self.t2.fwd(self.d2.fwd(ctx1), s2, rng)
-        _, f1s = self.f1.fwd(h1, rng, out=out1)
-        _, f2s = self.f2.fwd(h2, rng, out=out2)
-        return (s1, s2, q1, q2, ctx1, ctx2, a1s, a2s, t1s, t2s, f1s, f2s, Hb)
-
-    def bwd(self, dy1, dy2, saved, ds1, ds2):
-        s1, s2, q1, q2, ctx1, ctx2, a1s, a2s, t1s, t2s, f1s, f2s, Hb = saved
-        dh1 = self.f1.bwd(dy1, f1s)
-        dh2 = self.f2.bwd(dy2, f2s)
-        da1 = self.t1.bwd(dh1, t1s, ds1, dxsum=self.d1.gb)
-        da2 = self.t2.bwd(dh2, t2s, ds2, dxsum=self.d2.gb)
-        self.d1.wgrad(da1, ctx2, bias_done=True)
-        dctx2 = self.d1.dgrad(da1)
-        self.d2.wgrad(da2, ctx1, bias_done=True)
-        dctx1 = self.d2.dgrad(da2)
-        dq1 = torch.empty_like(q1)
-        dq2 = torch.empty_like(q2)
-        _attn_bwd(dctx1, ctx1, q2[:, 0:Hb], q1[:, Hb:2 * Hb], q1[:, 2 * Hb:], a1s, dq2[:, 0:Hb], dq1[:, Hb:2 * Hb],
-                  dq1[:, 2 * Hb:])
-        _attn_bwd(dctx2, ctx2, q1[:, 0:Hb], q2[:, Hb:2 * Hb], q2[:, 2 * Hb:], a2s, dq1[:, 0:Hb], dq2[:, Hb:2 * Hb],
-                  dq2[:, 2 * Hb:])
-        self.qkv1.wgrad(dq1, s1)
-        self.qkv1.dgrad(dq1, dx=ds1, beta=1.0)
-        self.qkv2.wgrad(dq2, s2)
-        self.qkv2.dgrad(dq2, dx=ds2, beta=1.0)
-
-
-    # ---- lock-step form: the same computation as fwd / bwd cut into segments at the GEMM stages, so
-    # the three co-attention blocks of one schedule step issue their (independent) GEMMs together and
-    # each stage runs as one grouped launch (_lockstep).  Inside a segment no op reads a GEMM output
-    # of the same segment.
-    def fwd_steps(self, s1, s2, nseq, l1, l2, mask1, mask2, rng, out1, out2, res):
+    # Cut into segments at the GEMM stages like BertLayerOp: the three co-attention blocks of one schedule step
+    # issue their (independent) GEMMs together and each stage runs as one grouped launch (_lockstep).
+    def fwd_steps(self, s1, s2, nseq, l1, l2, mask1, mask2, rng, out1, out2):
+        """-> saved; the outputs land in out1 / out2"""
         Hb = self.qkv1.W.shape[0] // 3
         q1 = self.qkv1.fwd(s1)
         q2 = self.qkv2.fwd(s2)
         yield
+        # ctx1: stream-2 queries over stream-1 keys (+ stream-1 mask); ctx2 the converse (:786-824)
         ctx1, a1s = ops.branch(_attn_fwd, q2[:, 0:Hb], q1[:, Hb:2 * Hb], q1[:, 2 * Hb:], mask1, nseq, l2, l1, self.nh,
                                self.pa1, rng)
         ctx2, a2s = ops.branch(_attn_fwd, q1[:, 0:Hb], q2[:, Hb:2 * Hb], q2[:, 2 * Hb:], mask2, nseq, l1, l2, self.nh,
@@ -497,7 +395,7 @@ class ConnectionOp(object):
         yield
         _, ts1 = self.f1.tail.fwd(o1, h1, rng, out=out1)
         _, ts2 = self.f2.tail.fwd(o2, h2, rng, out=out2)
-        res.append((s1, s2, q1, q2, ctx1, ctx2, a1s, a2s, t1s, t2s, (h1, u1, g1, ts1), (h2, u2, g2, ts2), Hb))
+        return (s1, s2, q1, q2, ctx1, ctx2, a1s, a2s, t1s, t2s, (h1, u1, g1, ts1), (h2, u2, g2, ts2), Hb)
 
     def bwd_steps(self, dy1, dy2, saved, ds1, ds2):
         s1, s2, q1, q2, ctx1, ctx2, a1s, a2s, t1s, t2s, f1s, f2s, Hb = saved
@@ -542,19 +440,37 @@ GROUP_TV = GROUPED and os.environ.get("K3M_GROUP_TV", "0") == "1"
 
 
 def _lockstep(gens):
-    """Run generators segment by segment; each round's GEMMs are issued under one ops.grouped()."""
-    live = list(gens)
+    """Run generators segment by segment; each round's GEMMs are issued under one ops.grouped().  Returns the
+    generators' return values, in order."""
+    live = list(enumerate(gens))
+    vals = [None] * len(live)
     while live:
         nxt = []
         with ops.grouped():
             with ops.branches():   # closes (main waits for the side streams) before the GEMM flush
-                for g in live:
+                for k, g in live:
                     try:
                         next(g)
-                        nxt.append(g)
-                    except StopIteration:
-                        pass
+                        nxt.append((k, g))
+                    except StopIteration as stop:
+                        vals[k] = stop.value
         live = nxt
+    return vals
+
+
+def _run(gen):
+    """Run one generator to its end outside any group, so every GEMM launches at once, on its own (k3m_gemm);
+    returns its return value.  Not _lockstep([gen]): a group of one is sized differently (ops._splitk)."""
+    try:
+        while True:
+            next(gen)
+    except StopIteration as stop:
+        return stop.value
+
+
+def _view(train):
+    """The op an engine runs: itself in training, its _eval_view otherwise."""
+    return (lambda op: op) if train else _eval_view
 
 
 def label_counts(batch):
@@ -746,6 +662,191 @@ class K3MEngine(object):
                 raise RuntimeError("stale labelled-row count hint %s: the labels hold %s (labels edited after "
                                    "collation, or a hand-built _label_counts)" % (hint, got))
 
+    # ------------------------------------------------------------ stages of both steps (this one and engine_text's)
+    def _struct_fwd(self, ctx, batch, seq_tp, c_init, rng, ent_neg, val_neg, groups):
+        """Structure aggregator + LPM (:2413-2505) over the PV rows of seq_tp; returns (c_final, LPM loss), the loss
+        None for a task other than pretraining (the encoder up to c_final only)."""
+        c, fp, dev = self.cfg, self.fp, self.device
+        B, T, P, H = ctx["B"], ctx["T"], ctx["P"], self.H
+        BT = B * T
+        index_p, index_v = batch["index_p"].contiguous(), batch["index_v"].contiguous()
+        NPV = index_p.shape[1]
+        X = torch.empty((B * NPV, 3 * H), dtype=torch.float32, device=dev)
+        nvalid = torch.empty((B,), dtype=torch.int32, device=dev)
+        src = torch.empty((B,), dtype=torch.int32, device=dev)
+        assert B % groups == 0
+        Bg = B // groups
+        for gi in range(groups):   # src (zero-triple fallback) is group-relative
+            r0 = gi * Bg
+            L.call("k3m_sa_gather", seq_tp[BT + r0 * P:].data_ptr(), index_p[r0:].data_ptr(), index_v[r0:].data_ptr(),
+                   c_init[r0:].data_ptr(), X[r0 * NPV:].data_ptr(), nvalid[r0:].data_ptr(), src[r0:].data_ptr(), Bg, P,
+                   NPV, H, L.F32, L.stream())
+        Tm = self.sw1.fwd(X)
+        att = torch.empty((B, NPV), dtype=torch.float32, device=dev)
+        agg = torch.empty((B, H), dtype=torch.float32, device=dev)
+        for gi in range(groups):
+            r0 = gi * Bg
+            L.call("k3m_sa_attn_fwd", Tm[r0 * NPV:].data_ptr(), nvalid[r0:].data_ptr(), src[r0:].data_ptr(),
+                   fp.p["struc_w2.weight"].data_ptr(), fp.p["struc_w2.bias"].data_ptr(), c_init[r0:].data_ptr(),
+                   att[r0:].data_ptr(), agg[r0:].data_ptr(), Bg, NPV, H, L.stream())
+        c_final = c_init.clone()
+        self.sw3.fwd(agg, out=c_final, beta=1.0)
+        ctx["groups"] = groups
+        ctx["batch"] = batch
+        if self.task != "pretrain":
+            ctx["struct"] = (X, nvalid, src, Tm, att, agg, c_init, c_final, None, None, None, index_p, index_v, NPV,
+                             None)
+            return c_final, None
+        assert groups == 1
+        nneg = int(getattr(c, "num_negative_pv", 4))
+        if ent_neg is None:
+            ke, kv = nneg // 2, nneg - nneg // 2   # vilbert_k3m.py:2476, :2488
+            ent_neg = torch.empty((B, NPV, ke), dtype=torch.int64, device=dev)
+            val_neg = torch.empty((B, NPV, kv), dtype=torch.int64, device=dev)
+            L.call("k3m_lpm_sample", nvalid.data_ptr(), B, NPV, ke, kv, rng.seed, rng.take(B * NPV * (ke + kv)),
+                   L.ptr(ent_neg), L.ptr(val_neg), L.stream())
+        else:
+            ent_neg = ent_neg.to(device=dev, dtype=torch.int64).contiguous()
+            val_neg = val_neg.to(device=dev, dtype=torch.int64).contiguous()
+            ke, kv = ent_neg.shape[2], val_neg.shape[2]
+        lpm = torch.empty((1,), dtype=torch.float32, device=dev)
+        lws = torch.empty((B * NPV * (2 * (ke + kv) + 1) + 2,), dtype=torch.float32, device=dev)
+        margin = float(getattr(c, "margin", 1.0))
+        L.call("k3m_lpm_fwd", c_final.data_ptr(), X.data_ptr(), nvalid.data_ptr(), L.ptr(ent_neg), L.ptr(val_neg), B, NPV,
+               H, ke, kv, margin, lpm.data_ptr(), lws.data_ptr(), L.stream())
+        ctx["struct"] = (X, nvalid, src, Tm, att, agg, c_init, c_final, ent_neg, val_neg, lws, index_p, index_v, NPV,
+                         margin)
+        return c_final, lpm
+
+    def _mlm_labels(self, ctx, batch):
+        """Compacts the masked-LM labels of the text and PV rows; returns ((row index, label, row scale, loss slot),
+        cnt).  cnt: device int32 [2], [0] the labelled-row count (the caller resolves it: a host hint or a sync),
+        [1] free for the caller's masked-region count."""
+        dev = self.device
+        B, T, P = ctx["B"], ctx["T"], ctx["P"]
+        BT, BP = B * T, B * P
+        nmax = BT + BP
+        # zero-filled: rows past the device count (a hint larger than the true count) gather row 0 with
+        # row_scale 0 and add nothing to any loss or gradient; a smaller hint is caught by check_hints
+        idx_m = torch.zeros((nmax,), dtype=torch.int32, device=dev)
+        lab_m = torch.zeros((nmax,), dtype=torch.int64, device=dev)
+        sc_m = torch.zeros((nmax,), dtype=torch.float32, device=dev)
+        sl_m = torch.zeros((nmax,), dtype=torch.int32, device=dev)
+        cnt = torch.zeros((2,), dtype=torch.int32, device=dev)
+        L.call("k3m_compact_labels_ex", batch["lm_label_ids"].contiguous().data_ptr(), BT, 0, T, T, 0, 0,
+               idx_m.data_ptr(), lab_m.data_ptr(), None, sc_m.data_ptr(), sl_m.data_ptr(), cnt.data_ptr(), L.stream())
+        L.call("k3m_compact_labels_ex", batch["lm_label_ids_pv"].contiguous().data_ptr(), BP, 0, P, P, BT, 1,
+               idx_m.data_ptr(), lab_m.data_ptr(), None, sc_m.data_ptr(), sl_m.data_ptr(), cnt.data_ptr(), L.stream())
+        return (idx_m, lab_m, sc_m, sl_m), cnt
+
+    def _mlm_head(self, ctx, seq_tp, labels, n_m, losses):
+        """MLM head on the n_m labelled rows of seq_tp (_mlm_labels): transform, LN, tied decoder, CE (which leaves
+        the logits' gradient in their place) and the two losses into losses[0:2].  Returns the captured logits
+        ({} unless capture_logits)."""
+        fp, dev, H = self.fp, self.device, self.H
+        idx_m, lab_m, sc_m, sl_m = labels
+        V = self.cfg.vocab_size
+        hm = torch.empty((n_m, H), dtype=torch.float32, device=dev)
+        ops.gather_rows(seq_tp, idx_m, n_m, hm)
+        pre_m = torch.empty_like(hm)
+        hm1 = self.mlm_t.fwd(hm, epi=L.EPI_BIAS_GELU, aux=pre_m)
+        hl = torch.empty_like(hm)
+        xh_m = torch.empty_like(hm)
+        rs_m = torch.empty((n_m,), dtype=torch.float32, device=dev)
+        if n_m:
+            ops.ln_fwd(hm1, None, self.mlm_ln.g, self.mlm_ln.b, hl, xh_m, rs_m)
+        E = fp.p["embeddings.word_embeddings.weight"] if self.dtype != "bf16" else fp.p16(
+            "embeddings.word_embeddings.weight")
+        logits = ops.linear(self._lo(hl), E, fp.p["cls.predictions.bias"], out_dtype=torch.float32)
+        # the CE kernel overwrites the logits with their gradient
+        captured = {"mlm_logits": logits.clone()} if self.capture_logits else {}
+        lr_m = torch.empty((n_m,), dtype=torch.float32, device=dev)
+        L.call("k3m_ce_fwd_bwd", logits.data_ptr(), V, lab_m.data_ptr(), sc_m.data_ptr(), n_m, V, lr_m.data_ptr(),
+               L.stream())
+        if n_m:
+            L.call("k3m_loss_reduce", lr_m.data_ptr(), sc_m.data_ptr(), sl_m.data_ptr(), n_m, losses.data_ptr(),
+                   L.stream())
+        ctx["mlm"] = (idx_m, n_m, hm, pre_m, hl, xh_m, rs_m, logits)
+        ctx["mlm_slot"] = sl_m   # 0: text row, 1: PV row (k3m_scale_rows_by_slot)
+        return captured
+
+    def _mlm_bwd(self, ctx, dseq_tp, w_mlm, w_mlm_pv):
+        """MLM head backward (dlogits already in place from the forward CE kernel): accumulates the head's
+        parameter gradients and adds the labelled rows' gradient into dseq_tp."""
+        fp, dev = self.fp, self.device
+        idx_m, n_m, hm, pre_m, hl, xh_m, rs_m, dlog = ctx["mlm"] if "mlm" in ctx else (None, 0) + (None,) * 6
+        if not n_m:
+            return
+        if w_mlm_pv is not None and w_mlm_pv != w_mlm:
+            # text and PV rows of the shared decoder carry different upstream weights: fold them into the rows
+            L.call("k3m_scale_rows_by_slot", dlog.data_ptr(), dlog.shape[1], ctx["mlm_slot"].data_ptr(), n_m,
+                   dlog.shape[1], w_mlm, w_mlm_pv, L.stream())
+            w_mlm = 1.0
+        bf = self.dtype == "bf16"
+        E = fp.p16("embeddings.word_embeddings.weight") if bf else fp.p["embeddings.word_embeddings.weight"]
+        gE = fp.g["embeddings.word_embeddings.weight"]
+        dlo = self._lo(dlog)
+        dhl = ops.linear_dgrad(dlo, E, dx=torch.empty(hl.shape, dtype=torch.float32, device=dev), alpha=w_mlm)
+        ops.linear_wgrad(dlo, self._lo(hl), gE, None, alpha=w_mlm)
+        ops.colsum(dlog, fp.g["cls.predictions.bias"], accumulate=True, alpha=w_mlm)
+        dh1 = torch.empty_like(hl)
+        ops.ln_bwd(dhl, xh_m, rs_m, self.mlm_ln.g, dh1, dh1, self.mlm_ln.gg, self.mlm_ln.gb)
+        du = torch.empty_like(hl)
+        ops.dgelu(dh1, pre_m, du)
+        self.mlm_t.wgrad(du, hm)
+        dhm = self.mlm_t.dgrad(du)
+        ops.scatter_add_rows(dhm, idx_m, n_m, dseq_tp)
+
+    def _struct_bwd(self, ctx, dseq_tp, w_lpm):
+        """Structure aggregator + LPM backward, with ctx["d_c_final"] / ctx["d_c_initial"] (a caller's upstream
+        gradients) added in: accumulates the struc_w* gradients, adds the PV rows' gradient into dseq_tp and
+        returns the gradient of c_initial."""
+        fp, dev, H = self.fp, self.device, self.H
+        B, T, P = ctx["B"], ctx["T"], ctx["P"]
+        (X, nvalid, src, Tm, att, agg, c_init, c_final, ent_neg, val_neg, lws, index_p, index_v, NPV,
+         margin) = ctx["struct"]
+        dcf = torch.zeros_like(c_final)
+        dX = torch.zeros_like(X)
+        det = ops.DETERMINISTIC   # fixed-order forms of the three kernels below (no float atomics)
+        if lws is not None:
+            if det:
+                L.call("k3m_lpm_bwd_det", c_final.data_ptr(), X.data_ptr(), nvalid.data_ptr(), L.ptr(ent_neg),
+                       L.ptr(val_neg), B, NPV, H, ent_neg.shape[2], val_neg.shape[2], lws.data_ptr(), dcf.data_ptr(),
+                       dX.data_ptr(), L.stream())
+            else:
+                L.call("k3m_lpm_bwd", c_final.data_ptr(), X.data_ptr(), nvalid.data_ptr(), L.ptr(ent_neg),
+                       L.ptr(val_neg), B, NPV, H, ent_neg.shape[2], val_neg.shape[2], margin, lws.data_ptr(),
+                       dcf.data_ptr(), dX.data_ptr(), L.stream())
+            if w_lpm != 1.0:
+                ops.add_(dcf, dcf.clone(), w_lpm - 1.0)
+                ops.add_(dX, dX.clone(), w_lpm - 1.0)
+        if "d_c_final" in ctx:
+            ops.add_(dcf, ctx["d_c_final"].contiguous())
+        dagg = self.sw3.dgrad(dcf)
+        self.sw3.wgrad(dcf, agg)
+        dci = dcf.clone()                                   # c_final = c_init + ...
+        if "d_c_initial" in ctx:
+            ops.add_(dci, ctx["d_c_initial"].contiguous())
+        dT = torch.zeros_like(Tm)
+        groups = ctx.get("groups", 1)
+        Bg = B // groups
+        sa_ws = torch.empty((Bg * (H + 1),), dtype=torch.float32, device=dev) if det else None
+        for gi in range(groups):
+            r0 = gi * Bg
+            sa = (dagg[r0:].data_ptr(), Tm[r0 * NPV:].data_ptr(), att[r0:].data_ptr(), nvalid[r0:].data_ptr(),
+                  src[r0:].data_ptr(), fp.p["struc_w2.weight"].data_ptr(), dT[r0 * NPV:].data_ptr(),
+                  fp.g["struc_w2.weight"].data_ptr(), fp.g["struc_w2.bias"].data_ptr(), dci[r0:].data_ptr())
+            if det:
+                L.call("k3m_sa_attn_bwd_det", *sa, sa_ws.data_ptr(), Bg, NPV, H, L.stream())
+            else:
+                L.call("k3m_sa_attn_bwd", *sa, Bg, NPV, H, L.stream())
+        self.sw1.wgrad(dT, X)
+        self.sw1.dgrad(dT, dx=dX, beta=1.0)
+        L.call("k3m_sa_gather_bwd_det" if det else "k3m_sa_gather_bwd", dX.data_ptr(), index_p.data_ptr(),
+               index_v.data_ptr(), nvalid.data_ptr(), dseq_tp[B * T:].data_ptr(), dci.data_ptr(), B, P, NPV, H, L.F32,
+               L.stream())
+        return dci
+
     def forward(self, batch, train=True, noise=None, ent_neg=None, val_neg=None, seed=None, groups=1):
         """Runs the forward of the step; returns (losses dict of device tensors, ctx for backward).
 
@@ -833,6 +934,7 @@ class K3MEngine(object):
         def partner(xt):
             return [(xt[0:BT], mt01), (xt[2 * BT:2 * BT + BP], mp01)] if self.dyn_attn else None
         enc = []
+        view = _view(train)
         sched = list(self.schedule)
         si = 0
         while si < len(sched):
@@ -845,20 +947,9 @@ class K3MEngine(object):
                 # image layer reads the text stream: independent only where the image layer comes first (after the
                 # last co-attention block; both then read the text state from before the pair)
                 pair = [(kind, i), nxt]
-                gens, outs = [], []
-                for k_, j_ in pair:
-                    op = self.text[j_] if k_ == "t" else self.image[j_]
-                    if not train:
-                        op = _eval_view(op)
-                    r = []
-                    outs.append(r)
-                    if k_ == "t":
-                        gens.append(op.fwd_steps(XT, tsegs, rng, r))
-                    else:
-                        gens.append(op.fwd_steps(XV, vsegs, rng, r, partner=partner(XT)))
-                _lockstep(gens)
-                for (k_, j_), r in zip(pair, outs):
-                    y, sv = r[0]
+                gens = [view(self.text[j_]).fwd_steps(XT, tsegs, rng) if k_ == "t" else
+                        view(self.image[j_]).fwd_steps(XV, vsegs, rng, partner=partner(XT)) for k_, j_ in pair]
+                for (k_, j_), (y, sv) in zip(pair, _lockstep(gens)):
                     if k_ == "t":
                         XT = y
                     else:
@@ -868,37 +959,25 @@ class K3MEngine(object):
                 continue
             si += 1
             if kind == "t":
-                op = self.text[i]
-                if not train:
-                    op = _eval_view(op)
                 if i < self.fixed_t:   # below the cut: forward-only, nothing kept
-                    XT = op.fwd_only(XT, tsegs, rng, save=not self.frozen_nosave)
+                    XT, _ = _run(view(self.text[i]).fwd_steps(XT, tsegs, rng, save=not self.frozen_nosave))
                     continue
-                XT, sv = op.fwd(XT, tsegs, rng)
+                XT, sv = _run(view(self.text[i]).fwd_steps(XT, tsegs, rng))
                 enc.append((kind, i, sv))
             elif kind == "v":
-                op = self.image[i]
-                if not train:
-                    op = _eval_view(op)
-                XV, sv = op.fwd(XV, vsegs, rng, partner=partner(XT))
+                XV, sv = _run(view(self.image[i]).fwd_steps(XV, vsegs, rng, partner=partner(XT)))
                 enc.append((kind, i, sv))
             else:
                 XT2 = torch.empty_like(XT)
                 XV2 = torch.empty_like(XV)
-                ops_ = [self.co_tv[i], self.co_pv[i], self.co_tt[i]]
-                if not train:
-                    ops_ = [_eval_view(o) for o in ops_]
+                ops_ = [view(o) for o in (self.co_tv[i], self.co_pv[i], self.co_tt[i])]
                 args = [(XV[0:BR], XT[0:BT], B, R, T, mask_v, mask_t, rng, XV2[0:BR], XT2[0:BT]),
                         (XV[BR:], XT[2 * BT:2 * BT + BP], B, R, P, mask_v, mask_p, rng, XV2[BR:],
                          XT2[2 * BT:2 * BT + BP]),
                         (XT[2 * BT + BP:], XT[BT:2 * BT], B, P, T, mask_p, mask_t, rng, XT2[2 * BT + BP:],
                          XT2[BT:2 * BT])]
-                if GROUPED:
-                    res = [[], [], []]
-                    _lockstep([o.fwd_steps(*a, res=r) for o, a, r in zip(ops_, args, res)])
-                    s_tv, s_pv, s_tt = res[0][0], res[1][0], res[2][0]
-                else:
-                    s_tv, s_pv, s_tt = [o.fwd(*a) for o, a in zip(ops_, args)]
+                gens = [o.fwd_steps(*a) for o, a in zip(ops_, args)]
+                s_tv, s_pv, s_tt = _lockstep(gens) if GROUPED else [_run(g) for g in gens]
                 enc.append((kind, i, (s_tv, s_pv, s_tt, ops_)))
                 XT, XV = XT2, XV2
         ctx["enc"] = enc
@@ -985,70 +1064,15 @@ class K3MEngine(object):
                c_init.numel(), L.F32, L.stream())
         ctx["pool"] = (mean_v,)
 
-        # ---- structure aggregator + LPM (:2413-2505)
-        index_p, index_v = batch["index_p"].contiguous(), batch["index_v"].contiguous()
-        NPV = index_p.shape[1]
-        X = torch.empty((B * NPV, 3 * H), dtype=torch.float32, device=dev)
-        nvalid = torch.empty((B,), dtype=torch.int32, device=dev)
-        src = torch.empty((B,), dtype=torch.int32, device=dev)
-        assert B % groups == 0
-        Bg = B // groups
-        for gi in range(groups):   # src (zero-triple fallback) is group-relative
-            r0 = gi * Bg
-            L.call("k3m_sa_gather", seq_tp[BT + r0 * P:].data_ptr(), index_p[r0:].data_ptr(), index_v[r0:].data_ptr(),
-                   c_init[r0:].data_ptr(), X[r0 * NPV:].data_ptr(), nvalid[r0:].data_ptr(), src[r0:].data_ptr(), Bg, P,
-                   NPV, H, L.F32, L.stream())
-        Tm = self.sw1.fwd(X)
-        att = torch.empty((B, NPV), dtype=torch.float32, device=dev)
-        agg = torch.empty((B, H), dtype=torch.float32, device=dev)
-        for gi in range(groups):
-            r0 = gi * Bg
-            L.call("k3m_sa_attn_fwd", Tm[r0 * NPV:].data_ptr(), nvalid[r0:].data_ptr(), src[r0:].data_ptr(),
-                   fp.p["struc_w2.weight"].data_ptr(), fp.p["struc_w2.bias"].data_ptr(), c_init[r0:].data_ptr(),
-                   att[r0:].data_ptr(), agg[r0:].data_ptr(), Bg, NPV, H, L.stream())
-        c_final = c_init.clone()
-        self.sw3.fwd(agg, out=c_final, beta=1.0)
-        if self.task != "pretrain":
-            ctx["struct"] = (X, nvalid, src, Tm, att, agg, c_init, c_final, None, None, None, index_p, index_v, NPV,
-                             None)
-            ctx["groups"] = groups
-            ctx["batch"] = batch
+        # ---- structure aggregator + LPM
+        c_final, lpm = self._struct_fwd(ctx, batch, seq_tp, c_init, rng, ent_neg, val_neg, groups)
+        if lpm is None:
             return {"c_initial": c_init, "c_final": c_final, "pooled_t": pooled_t, "pooled_pv": pooled_pv,
                     "pooled_v": pooled_v}, ctx
-        assert groups == 1
-        nneg = int(getattr(c, "num_negative_pv", 4))
-        if ent_neg is None:
-            ke, kv = nneg // 2, nneg - nneg // 2   # vilbert_k3m.py:2476, :2488
-            ent_neg = torch.empty((B, NPV, ke), dtype=torch.int64, device=dev)
-            val_neg = torch.empty((B, NPV, kv), dtype=torch.int64, device=dev)
-            L.call("k3m_lpm_sample", nvalid.data_ptr(), B, NPV, ke, kv, rng.seed, rng.take(B * NPV * (ke + kv)),
-                   L.ptr(ent_neg), L.ptr(val_neg), L.stream())
-        else:
-            ent_neg = ent_neg.to(device=dev, dtype=torch.int64).contiguous()
-            val_neg = val_neg.to(device=dev, dtype=torch.int64).contiguous()
-            ke, kv = ent_neg.shape[2], val_neg.shape[2]
-        lpm = torch.empty((1,), dtype=torch.float32, device=dev)
-        lws = torch.empty((B * NPV * (2 * (ke + kv) + 1) + 2,), dtype=torch.float32, device=dev)
-        margin = float(getattr(c, "margin", 1.0))
-        L.call("k3m_lpm_fwd", c_final.data_ptr(), X.data_ptr(), nvalid.data_ptr(), L.ptr(ent_neg), L.ptr(val_neg), B, NPV,
-               H, ke, kv, margin, lpm.data_ptr(), lws.data_ptr(), L.stream())
-        ctx["struct"] = (X, nvalid, src, Tm, att, agg, c_init, c_final, ent_neg, val_neg, lws, index_p, index_v, NPV,
-                         margin)
 
         # ---- heads on labelled rows only (unlabelled logits do not reach the loss or the gradients)
         losses = torch.zeros((4,), dtype=torch.float32, device=dev)   # mlm_t, mlm_pv, img, -
-        nmax = BT + BP
-        # zero-filled: rows past the device count (a hint larger than the true count) gather row 0 with
-        # row_scale 0 and add nothing to any loss or gradient; a smaller hint is caught by check_hints
-        idx_m = torch.zeros((nmax,), dtype=torch.int32, device=dev)
-        lab_m = torch.zeros((nmax,), dtype=torch.int64, device=dev)
-        sc_m = torch.zeros((nmax,), dtype=torch.float32, device=dev)
-        sl_m = torch.zeros((nmax,), dtype=torch.int32, device=dev)
-        cnt = torch.zeros((2,), dtype=torch.int32, device=dev)
-        L.call("k3m_compact_labels_ex", batch["lm_label_ids"].contiguous().data_ptr(), BT, 0, T, T, 0, 0,
-               idx_m.data_ptr(), lab_m.data_ptr(), None, sc_m.data_ptr(), sl_m.data_ptr(), cnt.data_ptr(), L.stream())
-        L.call("k3m_compact_labels_ex", batch["lm_label_ids_pv"].contiguous().data_ptr(), BP, 0, P, P, BT, 1,
-               idx_m.data_ptr(), lab_m.data_ptr(), None, sc_m.data_ptr(), sl_m.data_ptr(), cnt.data_ptr(), L.stream())
+        labels, cnt = self._mlm_labels(ctx, batch)
         R1 = R - 1
         idx_v = torch.zeros((B * R1,), dtype=torch.int32, device=dev)
         src_v = torch.zeros((B * R1,), dtype=torch.int32, device=dev)
@@ -1068,30 +1092,7 @@ class K3MEngine(object):
         else:
             n_m, n_v = [int(x) for x in cnt.tolist()]   # host sync (labelled-row counts)
 
-        V = c.vocab_size
-        hm = torch.empty((n_m, H), dtype=torch.float32, device=dev)
-        ops.gather_rows(seq_tp, idx_m, n_m, hm)
-        pre_m = torch.empty_like(hm)
-        hm1 = self.mlm_t.fwd(hm, epi=L.EPI_BIAS_GELU, aux=pre_m)
-        hl = torch.empty_like(hm)
-        xh_m = torch.empty_like(hm)
-        rs_m = torch.empty((n_m,), dtype=torch.float32, device=dev)
-        if n_m:
-            ops.ln_fwd(hm1, None, self.mlm_ln.g, self.mlm_ln.b, hl, xh_m, rs_m)
-        E = fp.p["embeddings.word_embeddings.weight"] if self.dtype != "bf16" else fp.p16(
-            "embeddings.word_embeddings.weight")
-        logits = ops.linear(self._lo(hl), E, fp.p["cls.predictions.bias"], out_dtype=torch.float32)
-        if self.capture_logits:   # the CE kernel overwrites the logits with their gradient
-            captured = {"mlm_logits": logits.clone()}
-        lr_m = torch.empty((n_m,), dtype=torch.float32, device=dev)
-        L.call("k3m_ce_fwd_bwd", logits.data_ptr(), V, lab_m.data_ptr(), sc_m.data_ptr(), n_m, V, lr_m.data_ptr(),
-               L.stream())
-        if n_m:
-            L.call("k3m_loss_reduce", lr_m.data_ptr(), sc_m.data_ptr(), sl_m.data_ptr(), n_m, losses.data_ptr(),
-                   L.stream())
-        ctx["mlm"] = (idx_m, n_m, hm, pre_m, hl, xh_m, rs_m, logits)
-        ctx["mlm_slot"] = sl_m   # 0: text row, 1: PV row (k3m_scale_rows_by_slot)
-
+        captured = self._mlm_head(ctx, seq_tp, labels, n_m, losses)
         Cv = c.v_target_size
         hv = torch.empty((n_v, Hv), dtype=torch.float32, device=dev)
         ops.gather_rows(seq_v, idx_v, n_v, hv)
@@ -1132,9 +1133,7 @@ class K3MEngine(object):
             "pooled_t": pooled_t, "pooled_pv": pooled_pv, "pooled_v": pooled_v,
         }
         out["loss"] = losses[0:1] + losses[1:2] + losses[2:3] + lpm
-        if self.capture_logits:
-            out.update(captured)
-        ctx["batch"] = batch
+        out.update(captured)
         return out, ctx
 
     # ------------------------------------------------------------ backward
@@ -1171,28 +1170,8 @@ class K3MEngine(object):
         dseq_tp = torch.zeros_like(seq_tp)
         dseq_v = torch.zeros_like(seq_v)
 
-        # ---- MLM head (dlogits already in place from the forward CE kernel)
-        idx_m, n_m, hm, pre_m, hl, xh_m, rs_m, dlog = ctx["mlm"] if "mlm" in ctx else (None, 0) + (None,) * 6
-        if n_m and w_mlm_pv is not None and w_mlm_pv != w_mlm:
-            # text and PV rows of the shared decoder carry different upstream weights: fold them into the rows
-            L.call("k3m_scale_rows_by_slot", dlog.data_ptr(), dlog.shape[1], ctx["mlm_slot"].data_ptr(), n_m,
-                   dlog.shape[1], w_mlm, w_mlm_pv, L.stream())
-            w_mlm = 1.0
-        if n_m:
-            bf = self.dtype == "bf16"
-            E = fp.p16("embeddings.word_embeddings.weight") if bf else fp.p["embeddings.word_embeddings.weight"]
-            gE = fp.g["embeddings.word_embeddings.weight"]
-            dlo = self._lo(dlog)
-            dhl = ops.linear_dgrad(dlo, E, dx=torch.empty(hl.shape, dtype=torch.float32, device=dev), alpha=w_mlm)
-            ops.linear_wgrad(dlo, self._lo(hl), gE, None, alpha=w_mlm)
-            ops.colsum(dlog, fp.g["cls.predictions.bias"], accumulate=True, alpha=w_mlm)
-            dh1 = torch.empty_like(hl)
-            ops.ln_bwd(dhl, xh_m, rs_m, self.mlm_ln.g, dh1, dh1, self.mlm_ln.gg, self.mlm_ln.gb)
-            du = torch.empty_like(hl)
-            ops.dgelu(dh1, pre_m, du)
-            self.mlm_t.wgrad(du, hm)
-            dhm = self.mlm_t.dgrad(du)
-            ops.scatter_add_rows(dhm, idx_m, n_m, dseq_tp)
+        # ---- heads, structure aggregator + LPM
+        self._mlm_bwd(ctx, dseq_tp, w_mlm, w_mlm_pv)
         idx_v, n_v, hv, pre_v, hlv, xh_iv, rs_iv, dlv = ctx["img"] if "img" in ctx else (None, 0) + (None,) * 6
         if n_v:
             dhlv = self.img_dec.dgrad(dlv, alpha=w_img)
@@ -1204,53 +1183,7 @@ class K3MEngine(object):
             self.img_t.wgrad(duv, hv)
             dhv = self.img_t.dgrad(duv)
             ops.scatter_add_rows(dhv, idx_v, n_v, dseq_v)
-
-        # ---- structure aggregator + LPM
-        (X, nvalid, src, Tm, att, agg, c_init, c_final, ent_neg, val_neg, lws, index_p, index_v, NPV,
-         margin) = ctx["struct"]
-        dcf = torch.zeros_like(c_final)
-        dX = torch.zeros_like(X)
-        det = ops.DETERMINISTIC   # fixed-order forms of the three kernels below (no float atomics)
-        if lws is not None:
-            if det:
-                L.call("k3m_lpm_bwd_det", c_final.data_ptr(), X.data_ptr(), nvalid.data_ptr(), L.ptr(ent_neg),
-                       L.ptr(val_neg), B, NPV, H, ent_neg.shape[2], val_neg.shape[2], lws.data_ptr(), dcf.data_ptr(),
-                       dX.data_ptr(), L.stream())
-            else:
-                L.call("k3m_lpm_bwd", c_final.data_ptr(), X.data_ptr(), nvalid.data_ptr(), L.ptr(ent_neg),
-                       L.ptr(val_neg), B, NPV, H, ent_neg.shape[2], val_neg.shape[2], margin, lws.data_ptr(),
-                       dcf.data_ptr(), dX.data_ptr(), L.stream())
-            if w_lpm != 1.0:
-                ops.add_(dcf, dcf.clone(), w_lpm - 1.0)
-                ops.add_(dX, dX.clone(), w_lpm - 1.0)
-        if "d_c_final" in ctx:
-            ops.add_(dcf, ctx["d_c_final"].contiguous())
-        dagg = self.sw3.dgrad(dcf)
-        self.sw3.wgrad(dcf, agg)
-        dci = dcf.clone()                                   # c_final = c_init + ...
-        if "d_c_initial" in ctx:
-            ops.add_(dci, ctx["d_c_initial"].contiguous())
-        dT = torch.zeros_like(Tm)
-        groups = ctx.get("groups", 1)
-        Bg = B // groups
-        sa_ws = torch.empty((Bg * (H + 1),), dtype=torch.float32, device=dev) if det else None
-        for gi in range(groups):
-            r0 = gi * Bg
-            if det:
-                L.call("k3m_sa_attn_bwd_det", dagg[r0:].data_ptr(), Tm[r0 * NPV:].data_ptr(), att[r0:].data_ptr(),
-                       nvalid[r0:].data_ptr(), src[r0:].data_ptr(), fp.p["struc_w2.weight"].data_ptr(),
-                       dT[r0 * NPV:].data_ptr(), fp.g["struc_w2.weight"].data_ptr(), fp.g["struc_w2.bias"].data_ptr(),
-                       dci[r0:].data_ptr(), sa_ws.data_ptr(), Bg, NPV, H, L.stream())
-            else:
-                L.call("k3m_sa_attn_bwd", dagg[r0:].data_ptr(), Tm[r0 * NPV:].data_ptr(), att[r0:].data_ptr(),
-                       nvalid[r0:].data_ptr(), src[r0:].data_ptr(), fp.p["struc_w2.weight"].data_ptr(),
-                       dT[r0 * NPV:].data_ptr(), fp.g["struc_w2.weight"].data_ptr(), fp.g["struc_w2.bias"].data_ptr(),
-                       dci[r0:].data_ptr(), Bg, NPV, H, L.stream())
-        self.sw1.wgrad(dT, X)
-        self.sw1.dgrad(dT, dx=dX, beta=1.0)
-        L.call("k3m_sa_gather_bwd_det" if det else "k3m_sa_gather_bwd", dX.data_ptr(), index_p.data_ptr(),
-               index_v.data_ptr(), nvalid.data_ptr(), dseq_tp[BT:].data_ptr(), dci.data_ptr(), B, P, NPV, H, L.F32,
-               L.stream())
+        dci = self._struct_bwd(ctx, dseq_tp, w_lpm)
 
         # ---- pooled outputs
         (mean_v,) = ctx["pool"]
@@ -1345,6 +1278,7 @@ class K3MEngine(object):
             dXT = ops.convert(dXT, torch.empty(dXT.shape, dtype=self.enc_dtype, device=dev))
             dXV = ops.convert(dXV, torch.empty(dXV.shape, dtype=self.enc_dtype, device=dev))
         renc = list(reversed(ctx["enc"]))
+        view = _view(ctx["train"])
 
         def dparts(dxt):   # the text-stream gradient rows the image layers' pools were taken from
             return [dxt[0:BT], dxt[2 * BT:2 * BT + BP]]
@@ -1355,22 +1289,16 @@ class K3MEngine(object):
             if GROUP_TV and nxt is not None and {kind, nxt[0]} == {"t", "v"} and not (self.dyn_attn and kind == "v"):
                 # (the pairs of the forward.)  Dynamic attention: the image layer's pool gradient belongs to the
                 # text state BEFORE the pair, i.e. to the gradient this text layer's backward produces: added below
-                gens, outs, pool_grads = [], [], []
-                for k_, j_, sv_ in (renc[ei], nxt):
-                    op = self.text[j_] if k_ == "t" else self.image[j_]
-                    if not ctx["train"]:
-                        op = _eval_view(op)
-                    r = []
-                    outs.append(r)
-                    # with dynamic attention the paired step keeps the unpaired step's bits (exact)
-                    gens.append(op.bwd_steps(dXT if k_ == "t" else dXV, sv_, r, exact=self.dyn_attn,
-                                             dyn_out=pool_grads))
-                _lockstep(gens)
-                for (k_, j_, _), r in zip((renc[ei], nxt), outs):
+                pool_grads = []
+                # with dynamic attention the paired step keeps the unpaired step's bits (exact)
+                gens = [view(self.text[j_] if k_ == "t" else self.image[j_]).bwd_steps(
+                    dXT if k_ == "t" else dXV, sv_, exact=self.dyn_attn, dyn_out=pool_grads)
+                    for k_, j_, sv_ in (renc[ei], nxt)]
+                for (k_, j_, _), dx in zip((renc[ei], nxt), _lockstep(gens)):
                     if k_ == "t":
-                        dXT = r[0]
+                        dXT = dx
                     else:
-                        dXV = r[0]
+                        dXV = dx
                 for pg in pool_grads:   # the image layer's, into the dXT the paired text layer just produced
                     pg.add_into(dparts(dXT))
                 if grad_ready is not None:
@@ -1380,12 +1308,10 @@ class K3MEngine(object):
                 continue
             ei += 1
             if kind == "t":
-                op = self.text[i] if ctx["train"] else _eval_view(self.text[i])
-                dXT = op.bwd(dXT, sv)
+                dXT = _run(view(self.text[i]).bwd_steps(dXT, sv))
             elif kind == "v":
-                op = self.image[i] if ctx["train"] else _eval_view(self.image[i])
                 pool_grads = []
-                dXV = op.bwd(dXV, sv, dyn_out=pool_grads)
+                dXV = _run(view(self.image[i]).bwd_steps(dXV, sv, dyn_out=pool_grads))
                 # below a cut with no text layer left to run backward the partner was computed without a graph: the
                 # pool gradient is dropped (dXT ends at the cut)
                 if self.fixed_t == 0 or any(k_ == "t" for k_, _, _ in renc[ei:]):
@@ -1398,11 +1324,12 @@ class K3MEngine(object):
                 bargs = [(dXV[0:BR], dXT[0:BT], s_tv, dXV2[0:BR], dXT2[0:BT]),
                          (dXV[BR:], dXT[2 * BT:2 * BT + BP], s_pv, dXV2[BR:], dXT2[2 * BT:2 * BT + BP]),
                          (dXT[2 * BT + BP:], dXT[BT:2 * BT], s_tt, dXT2[2 * BT + BP:], dXT2[BT:2 * BT])]
+                gens = [o.bwd_steps(*a) for o, a in zip(ops_, bargs)]
                 if GROUPED:
-                    _lockstep([o.bwd_steps(*a) for o, a in zip(ops_, bargs)])
+                    _lockstep(gens)
                 else:
-                    for o, a in zip(ops_, bargs):
-                        o.bwd(*a)
+                    for g in gens:
+                        _run(g)
                 dXT, dXV = dXT2, dXV2
             if grad_ready is not None:
                 grad_ready(kind, i)

@@ -7,7 +7,9 @@ calculate_for_two_text :1510), the fusion gate chooses between the individual st
 the NSP score uses ``pooled_t + pooled_pv`` (:1882-1883) and the image loss is a constant zero (:2815).  Only the
 hard gate (if_pre_sampling 1) is defined upstream for this model; K3MEngine refuses the others.
 
-A separate forward / backward pair over the op classes of k3m_amd/engine.py, so the tri-modal pair is untouched.
+A forward / backward pair of its own for the sections whose buffers differ from the tri-modal step's (embeddings,
+encoder loop, fusion gate, pooling), over the op classes and drivers of k3m_amd/engine.py; the structure aggregator
++ LPM and the MLM head, forward and backward, are K3MEngine's own methods, shared by both steps.
 Layout: ONE text buffer [B*T + B*P, 768] = [title | PV] — no duplicated streams (each stream has a single
 partner) and no image work.  The title and PV rows are adjacent in every fusion buffer, so relu-cat, gate and
 relu-split each run as one launch over both modalities; only the two scorer GEMMs (different weights) are per
@@ -21,10 +23,6 @@ from . import debug
 from . import _lib as L
 from . import engine as E
 from . import ops
-
-
-def _views(eng, train):
-    return (lambda op: op) if train else E._eval_view
 
 
 def forward(eng, batch, train=True, noise=None, ent_neg=None, val_neg=None, seed=None, groups=1):
@@ -63,25 +61,20 @@ def forward(eng, batch, train=True, noise=None, ent_neg=None, val_neg=None, seed
         XT = ops.convert(XT, torch.empty((Nt, H), dtype=ED, device=dev))
 
     # ---- encoder: text layers over (B, T) and (B, P); co_tt[i] alone at each ('c', i)
-    view = _views(eng, train)
+    view = E._view(train)
     tsegs = [(0, B, T, mask_t), (BT, B, P, mask_p)]
     enc = []
     for kind, i in eng.schedule:
         if kind == "t" and i < eng.fixed_t:   # below the fixed_t_layer cut: forward-only, nothing kept
-            XT = view(eng.text[i]).fwd_only(XT, tsegs, rng, save=not eng.frozen_nosave)
+            XT, _ = E._run(view(eng.text[i]).fwd_steps(XT, tsegs, rng, save=not eng.frozen_nosave))
         elif kind == "t":
-            XT, sv = view(eng.text[i]).fwd(XT, tsegs, rng)
+            XT, sv = E._run(view(eng.text[i]).fwd_steps(XT, tsegs, rng))
             enc.append((kind, i, sv))
         else:   # stream 1 = PV, stream 2 = title (BertConnectionLayer_two_text)
             op = view(eng.co_tt[i])
             XT2 = torch.empty_like(XT)
-            args = (XT[BT:], XT[0:BT], B, P, T, mask_p, mask_t, rng, XT2[BT:], XT2[0:BT])
-            if E.GROUPED:
-                res = []
-                E._lockstep([op.fwd_steps(*args, res=res)])
-                sv = res[0]
-            else:
-                sv = op.fwd(*args)
+            gen = op.fwd_steps(XT[BT:], XT[0:BT], B, P, T, mask_p, mask_t, rng, XT2[BT:], XT2[0:BT])
+            sv = E._lockstep([gen])[0] if E.GROUPED else E._run(gen)   # (a group of one is still a grouped launch)
             enc.append((kind, i, (sv, op)))
             XT = XT2
     ctx["enc"] = enc
@@ -117,93 +110,22 @@ def forward(eng, batch, train=True, noise=None, ent_neg=None, val_neg=None, seed
     c_init = torch.empty((B, H), **f32)
     L.call("k3m_mean2", pooled_t.data_ptr(), pooled_pv.data_ptr(), c_init.data_ptr(), c_init.numel(), L.F32, L.stream())
 
-    # ---- structure aggregator + LPM (:2413-2505), as the tri-modal step
-    index_p, index_v = batch["index_p"].contiguous(), batch["index_v"].contiguous()
-    NPV = index_p.shape[1]
-    X = torch.empty((B * NPV, 3 * H), **f32)
-    nvalid = torch.empty((B,), dtype=torch.int32, device=dev)
-    src = torch.empty((B,), dtype=torch.int32, device=dev)
-    assert B % groups == 0
-    Bg = B // groups
-    for gi in range(groups):   # src (zero-triple fallback) is group-relative
-        r0 = gi * Bg
-        L.call("k3m_sa_gather", seq_tp[BT + r0 * P:].data_ptr(), index_p[r0:].data_ptr(), index_v[r0:].data_ptr(),
-               c_init[r0:].data_ptr(), X[r0 * NPV:].data_ptr(), nvalid[r0:].data_ptr(), src[r0:].data_ptr(), Bg, P,
-               NPV, H, L.F32, L.stream())
-    Tm = eng.sw1.fwd(X)
-    att = torch.empty((B, NPV), **f32)
-    agg = torch.empty((B, H), **f32)
-    for gi in range(groups):
-        r0 = gi * Bg
-        L.call("k3m_sa_attn_fwd", Tm[r0 * NPV:].data_ptr(), nvalid[r0:].data_ptr(), src[r0:].data_ptr(),
-               fp.p["struc_w2.weight"].data_ptr(), fp.p["struc_w2.bias"].data_ptr(), c_init[r0:].data_ptr(),
-               att[r0:].data_ptr(), agg[r0:].data_ptr(), Bg, NPV, H, L.stream())
-    c_final = c_init.clone()
-    eng.sw3.fwd(agg, out=c_final, beta=1.0)
-    ctx["groups"] = groups
-    ctx["batch"] = batch
-    if eng.task != "pretrain":
-        ctx["struct"] = (X, nvalid, src, Tm, att, agg, c_init, c_final, None, None, None, index_p, index_v, NPV, None)
+    # ---- structure aggregator + LPM
+    c_final, lpm = eng._struct_fwd(ctx, batch, seq_tp, c_init, rng, ent_neg, val_neg, groups)
+    if lpm is None:
         return {"c_initial": c_init, "c_final": c_final, "pooled_t": pooled_t, "pooled_pv": pooled_pv,
                 "pooled_v": None}, ctx
-    assert groups == 1
-    nneg = int(getattr(c, "num_negative_pv", 4))
-    if ent_neg is None:
-        ke, kv = nneg // 2, nneg - nneg // 2   # vilbert_k3m.py:2476, :2488
-        ent_neg = torch.empty((B, NPV, ke), dtype=torch.int64, device=dev)
-        val_neg = torch.empty((B, NPV, kv), dtype=torch.int64, device=dev)
-        L.call("k3m_lpm_sample", nvalid.data_ptr(), B, NPV, ke, kv, rng.seed, rng.take(B * NPV * (ke + kv)),
-               L.ptr(ent_neg), L.ptr(val_neg), L.stream())
-    else:
-        ent_neg = ent_neg.to(device=dev, dtype=torch.int64).contiguous()
-        val_neg = val_neg.to(device=dev, dtype=torch.int64).contiguous()
-        ke, kv = ent_neg.shape[2], val_neg.shape[2]
-    lpm = torch.empty((1,), **f32)
-    lws = torch.empty((B * NPV * (2 * (ke + kv) + 1) + 2,), **f32)
-    margin = float(getattr(c, "margin", 1.0))
-    L.call("k3m_lpm_fwd", c_final.data_ptr(), X.data_ptr(), nvalid.data_ptr(), L.ptr(ent_neg), L.ptr(val_neg), B, NPV,
-           H, ke, kv, margin, lpm.data_ptr(), lws.data_ptr(), L.stream())
-    ctx["struct"] = (X, nvalid, src, Tm, att, agg, c_init, c_final, ent_neg, val_neg, lws, index_p, index_v, NPV,
-                     margin)
 
     # ---- MLM head on the labelled rows; slot 2 of `losses` (the image loss) stays an exact zero (:2815)
     losses = torch.zeros((4,), **f32)
-    idx_m = torch.zeros((Nt,), dtype=torch.int32, device=dev)
-    lab_m = torch.zeros((Nt,), dtype=torch.int64, device=dev)
-    sc_m = torch.zeros((Nt,), **f32)
-    sl_m = torch.zeros((Nt,), dtype=torch.int32, device=dev)
-    cnt = torch.zeros((2,), dtype=torch.int32, device=dev)
-    L.call("k3m_compact_labels_ex", batch["lm_label_ids"].contiguous().data_ptr(), BT, 0, T, T, 0, 0,
-           idx_m.data_ptr(), lab_m.data_ptr(), None, sc_m.data_ptr(), sl_m.data_ptr(), cnt.data_ptr(), L.stream())
-    L.call("k3m_compact_labels_ex", batch["lm_label_ids_pv"].contiguous().data_ptr(), BP, 0, P, P, BT, 1,
-           idx_m.data_ptr(), lab_m.data_ptr(), None, sc_m.data_ptr(), sl_m.data_ptr(), cnt.data_ptr(), L.stream())
+    labels, cnt = eng._mlm_labels(ctx, batch)
     hint = batch.get("_label_counts")
     if hint is not None:   # the region count of a loader's hint belongs to the unused image fields
         n_m = int(hint[0])
         eng._verify_hint((n_m, 0), cnt)
     else:
         n_m = int(cnt[0])   # host sync (labelled-row count)
-    V = c.vocab_size
-    hm = torch.empty((n_m, H), **f32)
-    ops.gather_rows(seq_tp, idx_m, n_m, hm)
-    pre_m = torch.empty_like(hm)
-    hm1 = eng.mlm_t.fwd(hm, epi=L.EPI_BIAS_GELU, aux=pre_m)
-    hl = torch.empty_like(hm)
-    xh_m = torch.empty_like(hm)
-    rs_m = torch.empty((n_m,), **f32)
-    if n_m:
-        ops.ln_fwd(hm1, None, eng.mlm_ln.g, eng.mlm_ln.b, hl, xh_m, rs_m)
-    bf = eng.dtype == "bf16"
-    Ew = fp.p16("embeddings.word_embeddings.weight") if bf else fp.p["embeddings.word_embeddings.weight"]
-    logits = ops.linear(eng._lo(hl), Ew, fp.p["cls.predictions.bias"], out_dtype=torch.float32)
-    captured = {"mlm_logits": logits.clone()} if eng.capture_logits else {}   # the CE kernel overwrites the logits
-    lr_m = torch.empty((n_m,), **f32)
-    L.call("k3m_ce_fwd_bwd", logits.data_ptr(), V, lab_m.data_ptr(), sc_m.data_ptr(), n_m, V, lr_m.data_ptr(),
-           L.stream())
-    if n_m:
-        L.call("k3m_loss_reduce", lr_m.data_ptr(), sc_m.data_ptr(), sl_m.data_ptr(), n_m, losses.data_ptr(), L.stream())
-    ctx["mlm"] = (idx_m, n_m, hm, pre_m, hl, xh_m, rs_m, logits)
-    ctx["mlm_slot"] = sl_m
+    captured = eng._mlm_head(ctx, seq_tp, labels, n_m, losses)
 
     nsp = torch.empty((1,), **f32)
     L.call("k3m_nsp_loss", pooled_t.data_ptr(), pooled_pv.data_ptr(), None,
@@ -233,73 +155,9 @@ def backward(eng, ctx, w_mlm=1.0, w_lpm=1.0, grad_ready=None, w_mlm_pv=None):
     dseq_tp = torch.zeros_like(seq_tp)
     f32 = dict(dtype=torch.float32, device=dev)
 
-    # ---- MLM head (dlogits already in place from the forward CE kernel)
-    idx_m, n_m, hm, pre_m, hl, xh_m, rs_m, dlog = ctx["mlm"] if "mlm" in ctx else (None, 0) + (None,) * 6
-    if n_m and w_mlm_pv is not None and w_mlm_pv != w_mlm:
-        L.call("k3m_scale_rows_by_slot", dlog.data_ptr(), dlog.shape[1], ctx["mlm_slot"].data_ptr(), n_m,
-               dlog.shape[1], w_mlm, w_mlm_pv, L.stream())
-        w_mlm = 1.0
-    if n_m:
-        bf = eng.dtype == "bf16"
-        Ew = fp.p16("embeddings.word_embeddings.weight") if bf else fp.p["embeddings.word_embeddings.weight"]
-        dlo = eng._lo(dlog)
-        dhl = ops.linear_dgrad(dlo, Ew, dx=torch.empty(hl.shape, **f32), alpha=w_mlm)
-        ops.linear_wgrad(dlo, eng._lo(hl), fp.g["embeddings.word_embeddings.weight"], None, alpha=w_mlm)
-        ops.colsum(dlog, fp.g["cls.predictions.bias"], accumulate=True, alpha=w_mlm)
-        dh1 = torch.empty_like(hl)
-        ops.ln_bwd(dhl, xh_m, rs_m, eng.mlm_ln.g, dh1, dh1, eng.mlm_ln.gg, eng.mlm_ln.gb)
-        du = torch.empty_like(hl)
-        ops.dgelu(dh1, pre_m, du)
-        eng.mlm_t.wgrad(du, hm)
-        dhm = eng.mlm_t.dgrad(du)
-        ops.scatter_add_rows(dhm, idx_m, n_m, dseq_tp)
-
-    # ---- structure aggregator + LPM
-    (X, nvalid, src, Tm, att, agg, c_init, c_final, ent_neg, val_neg, lws, index_p, index_v, NPV,
-     margin) = ctx["struct"]
-    dcf = torch.zeros_like(c_final)
-    dX = torch.zeros_like(X)
-    det = ops.DETERMINISTIC
-    if lws is not None:
-        if det:
-            L.call("k3m_lpm_bwd_det", c_final.data_ptr(), X.data_ptr(), nvalid.data_ptr(), L.ptr(ent_neg),
-                   L.ptr(val_neg), B, NPV, H, ent_neg.shape[2], val_neg.shape[2], lws.data_ptr(), dcf.data_ptr(),
-                   dX.data_ptr(), L.stream())
-        else:
-            L.call("k3m_lpm_bwd", c_final.data_ptr(), X.data_ptr(), nvalid.data_ptr(), L.ptr(ent_neg),
-                   L.ptr(val_neg), B, NPV, H, ent_neg.shape[2], val_neg.shape[2], margin, lws.data_ptr(),
-                   dcf.data_ptr(), dX.data_ptr(), L.stream())
-        if w_lpm != 1.0:
-            ops.add_(dcf, dcf.clone(), w_lpm - 1.0)
-            ops.add_(dX, dX.clone(), w_lpm - 1.0)
-    if "d_c_final" in ctx:
-        ops.add_(dcf, ctx["d_c_final"].contiguous())
-    dagg = eng.sw3.dgrad(dcf)
-    eng.sw3.wgrad(dcf, agg)
-    dci = dcf.clone()                                   # c_final = c_init + ...
-    if "d_c_initial" in ctx:
-        ops.add_(dci, ctx["d_c_initial"].contiguous())
-    dT = torch.zeros_like(Tm)
-    groups = ctx.get("groups", 1)
-    Bg = B // groups
-    sa_ws = torch.empty((Bg * (H + 1),), **f32) if det else None
-    for gi in range(groups):
-        r0 = gi * Bg
-        if det:
-            L.call("k3m_sa_attn_bwd_det", dagg[r0:].data_ptr(), Tm[r0 * NPV:].data_ptr(), att[r0:].data_ptr(),
-                   nvalid[r0:].data_ptr(), src[r0:].data_ptr(), fp.p["struc_w2.weight"].data_ptr(),
-                   dT[r0 * NPV:].data_ptr(), fp.g["struc_w2.weight"].data_ptr(), fp.g["struc_w2.bias"].data_ptr(),
-                   dci[r0:].data_ptr(), sa_ws.data_ptr(), Bg, NPV, H, L.stream())
-        else:
-            L.call("k3m_sa_attn_bwd", dagg[r0:].data_ptr(), Tm[r0 * NPV:].data_ptr(), att[r0:].data_ptr(),
-                   nvalid[r0:].data_ptr(), src[r0:].data_ptr(), fp.p["struc_w2.weight"].data_ptr(),
-                   dT[r0 * NPV:].data_ptr(), fp.g["struc_w2.weight"].data_ptr(), fp.g["struc_w2.bias"].data_ptr(),
-                   dci[r0:].data_ptr(), Bg, NPV, H, L.stream())
-    eng.sw1.wgrad(dT, X)
-    eng.sw1.dgrad(dT, dx=dX, beta=1.0)
-    L.call("k3m_sa_gather_bwd_det" if det else "k3m_sa_gather_bwd", dX.data_ptr(), index_p.data_ptr(),
-           index_v.data_ptr(), nvalid.data_ptr(), dseq_tp[BT:].data_ptr(), dci.data_ptr(), B, P, NPV, H, L.F32,
-           L.stream())
+    # ---- MLM head, structure aggregator + LPM
+    eng._mlm_bwd(ctx, dseq_tp, w_mlm, w_mlm_pv)
+    dci = eng._struct_bwd(ctx, dseq_tp, w_lpm)
 
     # ---- pooled outputs: c_initial = (pooled_t + pooled_pv) / 2
     dpt = torch.empty((B, H), **f32)
@@ -329,18 +187,18 @@ def backward(eng, ctx, w_mlm=1.0, w_lpm=1.0, grad_ready=None, w_mlm_pv=None):
     # ---- encoder, reversed
     if eng.enc_dtype != torch.float32:
         dXT = ops.convert(dXT, torch.empty(dXT.shape, dtype=eng.enc_dtype, device=dev))
-    view = _views(eng, ctx["train"])
+    view = E._view(ctx["train"])
     for kind, i, sv in reversed(ctx["enc"]):
         if kind == "t":
-            dXT = view(eng.text[i]).bwd(dXT, sv)
+            dXT = E._run(view(eng.text[i]).bwd_steps(dXT, sv))
         else:
             s, op = sv
             dXT2 = torch.empty_like(dXT)
-            args = (dXT[BT:], dXT[0:BT], s, dXT2[BT:], dXT2[0:BT])
+            gen = op.bwd_steps(dXT[BT:], dXT[0:BT], s, dXT2[BT:], dXT2[0:BT])
             if E.GROUPED:
-                E._lockstep([op.bwd_steps(*args)])
+                E._lockstep([gen])
             else:
-                op.bwd(*args)
+                E._run(gen)
             dXT = dXT2
         if grad_ready is not None:
             grad_ready(kind, i)

@@ -9,9 +9,9 @@ with the reference's rate per site, read from the config (vilbert_k3m.py: attent
 
 Checked, per layer kind (text BertLayer 12 heads x 64, image BertImageLayer 8 x 128, the 1024-bi
 co-attention layer image x text (37 x 36) and image x PV (37 x 128), the two-text co-attention PV x text
-(8 heads x 96, 128 x 36), each also through the lock-step path the engine runs (fwd_steps / bwd_steps
-under engine._lockstep, grouped GEMM launches), and the text / image embeddings with their output
-dropout): forward output, input gradient(s) and the parameter gradients against a float64 autograd
+(8 heads x 96, 128 x 36), each through both drivers of its one step-form body (fwd_steps / bwd_steps): alone
+under engine._run (every GEMM launched at once) and under engine._lockstep (grouped GEMM launches); and the
+text / image embeddings with their output dropout): forward output, input gradient(s) and the parameter gradients against a float64 autograd
 reference (fp32 kernels: 2e-4 of each tensor's scale)."""
 import numpy as np
 import pytest
@@ -66,10 +66,10 @@ def _lengths_mask(nseq, L, g):
     return (torch.arange(L)[None, :] < lens[:, None]).long()
 
 
-@pytest.mark.parametrize("kind", ["text", "image"])
-def test_bert_layer_train_mode(eng, kind):
+@pytest.mark.parametrize("kind,lockstep", [("text", False), ("text", True), ("image", False), ("image", True)])
+def test_bert_layer_train_mode(eng, kind, lockstep):
     from oracle import k3m_oracle as O
-    from k3m_amd.engine import Rng, _ext_mask
+    from k3m_amd.engine import Rng, _ext_mask, _lockstep, _run
     c = eng.cfg
     if kind == "text":
         op, pre, H, nh, L = eng.text[4], "encoder.layer.4", c.hidden_size, c.num_attention_heads, 36
@@ -85,9 +85,15 @@ def test_bert_layer_train_mode(eng, kind):
     dev = torch.device("cuda")
     eng.fp.grad.zero_()
     rng = Rng(seed)
-    y, saved = op.fwd(x.to(dev), [(0, nseq, L, _ext_mask(m.to(dev)))], rng)
-    dx = op.bwd(dy.to(dev), saved)
+    fwd = op.fwd_steps(x.to(dev), [(0, nseq, L, _ext_mask(m.to(dev)))], rng)
+    if lockstep:
+        (y, saved), = _lockstep([fwd])
+        dx, = _lockstep([op.bwd_steps(dy.to(dev), saved)])
+    else:
+        y, saved = _run(fwd)
+        dx = _run(op.bwd_steps(dy.to(dev), saved))
     torch.cuda.synchronize()
+    kind += " lockstep" if lockstep else ""
     # the layer's counters: attention probabilities, then the two residual tails (Rng.take order)
     na, nh_ = nseq * nh * L * L, nseq * L * H
     drop = {"attn": torch.from_numpy(DM.attn_keep_scale(rng.seed, 0, nseq * nh * L, L, pa)),
@@ -126,7 +132,7 @@ def _co_rates(c, kind):
 @pytest.mark.parametrize("kind,lockstep", [("tv", False), ("tv", True), ("pv", True), ("tt", False), ("tt", True)])
 def test_coattention_layer_train_mode(eng, kind, lockstep):
     from oracle import k3m_oracle as O
-    from k3m_amd.engine import Rng, _ext_mask, _lockstep
+    from k3m_amd.engine import Rng, _ext_mask, _lockstep, _run
     c = eng.cfg
     ops_name, pre, L1, L2, w1, w2 = CO_KINDS[kind]
     op = getattr(eng, ops_name)[int(pre.rsplit(".", 1)[1])]
@@ -147,13 +153,11 @@ def test_coattention_layer_train_mode(eng, kind, lockstep):
     ds2 = torch.empty(nseq * L2, H2, device=dev)
     args = (s1.to(dev), s2.to(dev), nseq, L1, L2, _ext_mask(m1.to(dev)), _ext_mask(m2.to(dev)), rng, o1, o2)
     if lockstep:
-        res = []
-        _lockstep([op.fwd_steps(*args, res)])
-        saved = res[0]
+        saved, = _lockstep([op.fwd_steps(*args)])
         _lockstep([op.bwd_steps(dy1.to(dev), dy2.to(dev), saved, ds1, ds2)])
     else:
-        saved = op.fwd(*args)
-        op.bwd(dy1.to(dev), dy2.to(dev), saved, ds1, ds2)
+        saved = _run(op.fwd_steps(*args))
+        _run(op.bwd_steps(dy1.to(dev), dy2.to(dev), saved, ds1, ds2))
     torch.cuda.synchronize()
     # counters in ConnectionOp order: probs1 (stream-2 queries over stream-1 keys), probs2, BiOutput tails
     # 1 and 2, stream-1 FFN tail, stream-2 FFN tail
