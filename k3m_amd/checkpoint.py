@@ -3,7 +3,8 @@
 The reference writes, per epoch (train_concap_struc.py:691-705):
 
 * ``K3M_struc_presample-<p>_epoch-<e>.bin``: ``model.state_dict()`` — 999 keys, the 998 parameters
-  of ``named_parameters()`` plus the tied ``cls.predictions.decoder.weight`` (vilbert_k3m.py:2266-2272);
+  of ``named_parameters()`` plus the tied ``cls.predictions.decoder.weight`` (vilbert_k3m.py:2266-2272); 351 keys
+  (350 parameters) for the model without co-attention, the drivers' default;
 * ``...tar``: ``{"model_state_dict", "optimizer_state_dict", "scheduler_state_dict", "global_step"}``
 
 and reads them back with ``module.`` stripped (:259-297).  The optimizer is pytorch_transformers'
@@ -11,7 +12,7 @@ AdamW over the two parameter groups of :352-367 (weights with decay 0.01 first, 
 "bias"/"LayerNorm.*" names with 0.0, each in ``named_parameters()`` order); its
 ``state_dict()`` is torch.optim.Optimizer's: parameters numbered consecutively across the groups,
 per-parameter state ``{"step", "exp_avg", "exp_avg_sq"}`` only for parameters that received a
-gradient (the 86 never-grad tensors have none).  The scheduler is WarmupLinearSchedule, a LambdaLR
+gradient (the never-grad tensors — 86, or 14 without co-attention — have none).  The scheduler is WarmupLinearSchedule, a LambdaLR
 (``warmup_steps``, ``t_total``, ``base_lrs``, ``last_epoch`` ...).
 
 Here the parameters and the AdamW moments live in flat HBM buffers (k3m_amd/params.py,
@@ -53,7 +54,8 @@ def _groups_of_trainer(trainer):
 
 
 def model_state_dict(fp):
-    """CPU copy of the 999-key reference state_dict."""
+    """CPU copy of the reference state_dict: named_parameters() plus, for the pretraining model, the tied decoder
+    (999 keys by default, 351 without co-attention)."""
     sd = {}
     for name, _ in fp.spec:
         sd[name] = fp.p[name].detach().to("cpu", copy=True)
@@ -98,6 +100,24 @@ def check_dynamic_attention(names, sd):
                          % len(sd))
 
 
+COATT_KEY = "encoder.c_layer_pv_t.0.biattention.query1.weight"   # present exactly with co-attention (any modality set)
+
+
+def check_coattention(names, sd):
+    """Refuse a state dict with the connection blocks (encoder.c_layer*) for a model built without co-attention
+    (with_coattention false: BertEncoder registers none of them, vilbert_k3m.py:1143-1152) and the reverse, before
+    anything is copied: every tensor the two models share has the same name and shape, so a non-strict load would
+    drop the blocks (or leave them at their initial values) and run another model than the file's."""
+    model_has, file_has = COATT_KEY in set(names), COATT_KEY in sd
+    if file_has and not model_has:
+        raise ValueError("the state dict holds the co-attention blocks (encoder.c_layer*, %d keys) but this model was "
+                         "built without co-attention (with_coattention=False); nothing was loaded" % len(sd))
+    # an encoder-only file (a BERT checkpoint for --pretrained_model_path) has no fusion scorer and passes
+    if model_has and not file_has and "score_self_t.weight" in sd:
+        raise ValueError("this model was built with co-attention (with_coattention=True) but the state dict (%d keys) "
+                         "is of a model without the encoder.c_layer* blocks; nothing was loaded" % len(sd))
+
+
 def check_shapes(fp, sd):
     """Every tensor of ``sd`` that the model has must have the model's shape (checked before the first copy)."""
     for name, _ in fp.spec:
@@ -111,6 +131,7 @@ def load_model_state_dict(fp, sd, strict=True):
     sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
     check_modalities([n for n, _ in fp.spec], sd)
     check_dynamic_attention([n for n, _ in fp.spec], sd)
+    check_coattention([n for n, _ in fp.spec], sd)
     missing = [n for n, _ in fp.spec if n not in sd]
     if strict and missing:
         raise KeyError("state_dict lacks %d parameters, e.g. %s" % (len(missing), missing[:4]))

@@ -517,6 +517,17 @@ def validate_config(cfg):
                          "self.num_negative, which no constructor sets (vilbert_k3m.py:2764-2765)")
     if vt not in (0, 1):
         raise ValueError("visual_target=%r: the reference defines 0 (KL), 1 (feature regression) and 2 (NCE)" % (vt,))
+    if getattr(cfg, "in_batch_pairs", False):
+        raise ValueError("in_batch_pairs=True is not built: it expands the streams to B x B text/image pairs before the "
+                         "first connection block (vilbert_k3m.py:1228-1260), which the wide buffers have no rows for; "
+                         "no driver of the reference sets it")
+    if getattr(cfg, "fast_mode", False):
+        raise ValueError("fast_mode=True is not built: it broadcasts the text stream over the image batch before the "
+                         "first connection block (vilbert_k3m.py:1262-1273); no driver of the reference sets it")
+    if getattr(cfg, "model", "bert") not in ("bert", "roberta"):
+        raise ValueError("model=%r: the reference's embeddings know 'bert' and 'roberta' only" % (cfg.model,))
+    # with_coattention False (the reference drivers' default: --with_coattention is store_true) is the model
+    # without the connection blocks (vilbert_k3m.py:1143-1152, :1275, :1453, :1629): accepted
 
 
 class K3MEngine(object):
@@ -554,9 +565,9 @@ class K3MEngine(object):
         self.frozen_nosave = os.environ.get("K3M_FROZEN_NOSAVE", "1") != "0"
         # the tensors that are never-grad because of the cut alone (the module surface leaves their .grad None)
         self.cut_frozen = fp.frozen - {n for n, _ in fp.spec if is_frozen(n, _without_cut(c))} if self.fixed_t else set()
-        assert not getattr(c, "in_batch_pairs", False) and not getattr(c, "fast_mode", False)
-        assert getattr(c, "model", "bert") in ("bert", "roberta")
-        assert c.with_coattention
+        # False: no connection blocks (the reference registers none, vilbert_k3m.py:1143-1152): the schedule has no
+        # ('c', i) entry and the two copies of a stream differ by their dropout draws alone
+        self.coattn = bool(c.with_coattention)
         self.visual_target = int(getattr(c, "visual_target", 0))
         # False: the model without the image modality — the forward / backward pair of k3m_amd/engine_text.py
         self.use_image = bool(getattr(c, "use_image", True))
@@ -572,6 +583,8 @@ class K3MEngine(object):
                      for i in range(c.num_hidden_layers)]
         nco = len(c.v_biattention_id)
         nb = c.bi_num_attention_heads
+        if not self.coattn:   # their parameters do not exist
+            nco = 0
         self.co_tt = [ConnectionOp(fp, "encoder.c_layer_pv_t.%d" % i, nb, self.p_va, self.p_a, self.p_vh, self.p_h,
                                    self.p_h, self.p_h) for i in range(nco)]
         self.emb_ln = LN(fp, "embeddings.LayerNorm")
@@ -617,14 +630,18 @@ class K3MEngine(object):
     # ------------------------------------------------------------ encoder schedule
     def _schedule(self):
         """[(kind, index)] in lock-step order: ('t', i) text layer on all four text/PV streams,
-        ('v', i) image layer on both image streams, ('c', i) co-attention block i."""
+        ('v', i) image layer on both image streams, ('c', i) co-attention block i.  Without co-attention the
+        ('c', i) entries are left out and the t / v order stays the reference loop's (vilbert_k3m.py:1185-1290): in
+        iteration i the text layers below t_biattention_id[i], then the image layers below v_biattention_id[i]
+        (observable with dynamic attention, where an image layer reads the text state)."""
         c = self.cfg
         sch = []
         t0 = v0 = 0
         for i, (v1, t1) in enumerate(zip(c.v_biattention_id, c.t_biattention_id)):
             sch += [("t", k) for k in range(t0, t1)]
             sch += [("v", k) for k in range(v0, v1)]
-            sch.append(("c", i))
+            if self.coattn:
+                sch.append(("c", i))
             t0, v0 = t1, v1
         sch += [("v", k) for k in range(v0, c.v_num_hidden_layers)]
         sch += [("t", k) for k in range(t0, c.num_hidden_layers)]

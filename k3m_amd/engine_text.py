@@ -61,6 +61,7 @@ def forward(eng, batch, train=True, noise=None, ent_neg=None, val_neg=None, seed
         XT = ops.convert(XT, torch.empty((Nt, H), dtype=ED, device=dev))
 
     # ---- encoder: text layers over (B, T) and (B, P); co_tt[i] alone at each ('c', i)
+    # (no such entry without co-attention: every stream once, text layers only)
     view = E._view(train)
     tsegs = [(0, B, T, mask_t), (BT, B, P, mask_p)]
     enc = []

@@ -3,7 +3,9 @@
 The names, shapes and order reproduce ``named_parameters()`` of the reference model
 (module registration order: vilbert_k3m.py:2190-2264; per-module layouts :335-1152, :1753-1924,
 :2141-2161), so ``state_dict()`` files interchange (999 keys incl. the tied
-``cls.predictions.decoder.weight``).
+``cls.predictions.decoder.weight``; 351 keys / 350 parameters without co-attention, ``cfg.with_coattention`` false:
+BertEncoder registers no ``c_layer*``, vilbert_k3m.py:1143-1152, and the 72 ``q_dense*`` tensors leave the never-grad
+set with them: 14 tensors in modes 0 and 1).
 
 MI355X layout: every parameter is a view into ONE contiguous fp32 buffer (``FlatParams``), and so
 is every gradient (a second buffer of the same size).  Consequences:

@@ -77,10 +77,11 @@ class BertForMultiModalPreTraining_tri_stru(nn.Module):
         return {k: v.detach() for k, v in sd.items()}
 
     def load_state_dict(self, state_dict, strict=True):
-        from .checkpoint import check_dynamic_attention, check_modalities, check_shapes
+        from .checkpoint import check_coattention, check_dynamic_attention, check_modalities, check_shapes
         sd = {k[7:] if k.startswith("module.") else k: v for k, v in state_dict.items()}
         check_modalities(self._names, sd)   # tri-modal file into a model without the image modality, or the reverse
         check_dynamic_attention(self._names, sd)   # dyLinear_* gates into a model without them, or the reverse
+        check_coattention(self._names, sd)   # encoder.c_layer* blocks into a model without them, or the reverse
         missing = [n for n in self._names if n not in sd]
         if strict and missing:
             raise KeyError("missing keys: %s" % missing[:8])
@@ -147,6 +148,8 @@ class BertForMultiModalPreTraining_tri_stru(nn.Module):
 
     def _expose_grads(self):
         cut = self.engine.cut_frozen   # below a fixed_t_layer cut: no gradient, as under the reference's no_grad
+        if not self.engine.coattn:   # the model without co-attention: .grad stays None on its 14 never-grad tensors
+            cut = cut | self.engine.fp.frozen
         for n in self._names:
             p = getattr(self, n.replace(".", "__"))
             if n in cut:

@@ -12,7 +12,10 @@ Dropout is off and the gumbel noise / LPM negatives are explicit, so a rank's se
 repeats its first.  Both ranks may share one GPU (``--backend gloo``); with one GPU per rank use nccl
 (RCCL).  The parent never touches the GPU (the ranks are child processes).  Prints one JSON line.
 
-    python scripts/ddp_engine_check.py [--world 2] [--backend gloo] [--batch 2]
+    python scripts/ddp_engine_check.py [--world 2] [--backend gloo] [--batch 2] [--no_coattention]
+
+``--no_coattention``: the model without the connection blocks (with_coattention=False) — the shorter schedule, no
+('c', i) bucket; the encoder.c_layer* names of the tensor check are left out.
 """
 import argparse
 import json
@@ -32,7 +35,11 @@ NAMES = ["cls.predictions.transform.dense.weight", "struc_w1.weight", "score_sel
          "v_embeddings.image_embeddings.weight"]
 
 
-def _worker(rank, world, port, backend, batch_size, out, dtype="fp32"):
+def _names(coattn):
+    return [n for n in NAMES if coattn or ".c_layer" not in n]
+
+
+def _worker(rank, world, port, backend, batch_size, out, dtype="fp32", coattn=True):
     import torch
     import torch.distributed as dist
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -48,7 +55,8 @@ def _worker(rank, world, port, backend, batch_size, out, dtype="fp32"):
     from k3m_amd.ddp import GradAllReducer
     from k3m_amd.synthetic import synthetic_batch, synthetic_noise
     from k3m_amd.trainer import Trainer
-    cfg = pretrain_config(os.path.join(REPO, "configs", "bert_base_6layer_6conect.json"))
+    cfg = pretrain_config(os.path.join(REPO, "configs", "bert_base_6layer_6conect.json"), with_coattention=coattn)
+    NAMES = _names(coattn)
     cfg.hidden_dropout_prob = cfg.attention_probs_dropout_prob = 0.0
     cfg.v_hidden_dropout_prob = cfg.v_attention_probs_dropout_prob = 0.0
     B = batch_size
@@ -113,7 +121,9 @@ def main():
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"],
                     help="bf16: bf16 encoder and bf16 gradient buckets (reduced-gradient tolerance 1e-2)")
+    ap.add_argument("--no_coattention", action="store_true", help="the model without the connection blocks")
     a = ap.parse_args()
+    NAMES = _names(not a.no_coattention)
     import torch
     import torch.multiprocessing as mp
     s = socket.socket()
@@ -121,11 +131,13 @@ def main():
     port = s.getsockname()[1]
     s.close()
     out = tempfile.mkdtemp(prefix="k3m_ddp_")
-    mp.spawn(_worker, args=(a.world, port, a.backend, a.batch, out, a.dtype), nprocs=a.world, join=True)
+    mp.spawn(_worker, args=(a.world, port, a.backend, a.batch, out, a.dtype, not a.no_coattention),
+             nprocs=a.world, join=True)
     R = [torch.load(os.path.join(out, "r%d.pt" % r), weights_only=True) for r in range(a.world)]
     sched = R[0]["schedule"]
     expected = [["head", 0]] + [[k, i] for k, i in reversed(sched)] + [["emb", 0]]
     res = {"world": a.world, "backend": a.backend, "dtype": a.dtype, "world_seen": R[0]["world_seen"],
+           "with_coattention": not a.no_coattention, "blocks": len(expected),
            "order_ok": all(r["order"] == expected for r in R), "order_rank0": R[0]["order"][:6] + ["..."]}
     worst = 0.0
     for n in NAMES:
