@@ -135,6 +135,14 @@ int k3m_embed_fwd(const int64_t* ids, const int64_t* tt, const float* word, cons
                   const float* gamma, const float* beta, void* y0, void* y1, void* y2, void* xhat, float* rstd,
                   int nseq, int len, int hidden, float eps, float p_out, uint64_t seed, uint64_t off,
                   int dtype, hipStream_t stream);
+/* xhat == rstd == NULL: the forward-only form (a kernel instantiation without the two stores; y bit-identical);
+ * one of the two alone is K3M_EINVAL.  k3m_embed_fwd_ex: y1 / y2 in y1_dtype -- K3M_BF16 beside dtype K3M_F32
+ * writes the encoder copies in bf16 (the bits of k3m_convert of the fp32 row) while y0 stays fp32; forward-only
+ * form only (K3M_EINVAL with xhat).  y1_dtype == dtype is k3m_embed_fwd. */
+int k3m_embed_fwd_ex(const int64_t* ids, const int64_t* tt, const float* word, const float* pos, const float* type,
+                     const float* gamma, const float* beta, void* y0, void* y1, void* y2, void* xhat, float* rstd,
+                     int nseq, int len, int hidden, float eps, float p_out, uint64_t seed, uint64_t off, int dtype,
+                     int y1_dtype, hipStream_t stream);
 /* Gradient of the lookup: dword[id] += ds (skipping id 0: padding_idx, :343-345), dpos, dtype.
  * ds = d(pre-LN sum) from k3m_ln_bwd. */
 int k3m_embed_bwd(const int64_t* ids, const int64_t* tt, const void* ds, float* dword, float* dpos, float* dtype_,
@@ -244,7 +252,9 @@ int k3m_nsp_loss(const float* pt, const float* ppv, const float* pv, const float
 int k3m_relu_cat3(const void* x0, const void* x1, const void* x2, void* c, int rows, int d, int dtype,
                   hipStream_t stream);
 /* gate forward: a = sigmoid scores [rows, 3D]; noise [rows, 3, D] or NULL (then gumbel noise is
- * drawn from (seed, off)); ys = softmax(a + g) over the 3 streams; idx = argmax; out = c[idx]. */
+ * drawn from (seed, off)); ys = softmax(a + g) over the 3 streams; idx = argmax; out = c[idx].
+ * ys == idx == NULL (here and in k3m_gate2_fwd): the forward-only form, a kernel instantiation without the two
+ * stores -- the same draws and the same out; one of the two alone is K3M_EINVAL. */
 int k3m_gate_fwd(const float* a, const void* c, const float* noise, float* ys, uint8_t* idx, void* out, int rows,
                  int d, uint64_t seed, uint64_t off, int dtype, hipStream_t stream);
 /* gate backward (straight-through): dc = onehot*dout; dpre = sigmoid'(a)*softmax'(ys)(dout*c). */
@@ -446,6 +456,13 @@ int k3m_align_ce_fwd_bwd(const float* u, const float* W, const float* bias, cons
  * de [2B][H] = d loss / d e (written). */
 int k3m_align_cosine_fwd_bwd(const float* e, const float* labels, int B, int H, float margin, float* loss,
                              float* probs, float* loss_rows, float* de, hipStream_t stream);
+/* Forward-only forms of the two heads (prediction): the same row-kernel bodies without any gradient store;
+ * logits / probs / loss_rows / loss carry the bits of the fwd_bwd forms. */
+int k3m_align_ce_fwd(const float* u, const float* W, const float* bias, const float* labels, int B, int H, float p,
+                     uint64_t seed, uint64_t off, float* logits, float* probs, float* loss_rows, float* loss,
+                     hipStream_t stream);
+int k3m_align_cosine_fwd(const float* e, const float* labels, int B, int H, float margin, float* loss, float* probs,
+                         float* loss_rows, hipStream_t stream);
 
 /* ---- Data path ------------------------------------------------------
  * Global-region collation of a batch of region features, fused with mask_region's feature

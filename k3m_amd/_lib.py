@@ -46,6 +46,8 @@ SIGNATURES = {
     "k3m_colsum_slabs": [vp, i64, i32, i32, vp, i32, vp],
     "k3m_slab_reduce_batch": [vp, vp, vp, vp, vp, i32, vp],
     "k3m_embed_fwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, u64, u64, i32, vp],
+    "k3m_embed_fwd_ex": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, u64, u64, i32, i32,
+                         vp],
     "k3m_embed_bwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "k3m_attn_fwd": [vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32, i32, f32, f32, u64, u64, i32, vp],
     "k3m_attn_bwd": [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, i32,
@@ -120,6 +122,8 @@ SIGNATURES = {
     "k3m_align_pair_cat_bwd": [vp, i32, i32, f32, u64, u64, vp, vp],
     "k3m_align_ce_fwd_bwd": [vp, vp, vp, vp, i32, i32, f32, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "k3m_align_cosine_fwd_bwd": [vp, vp, i32, i32, f32, vp, vp, vp, vp, vp],
+    "k3m_align_ce_fwd": [vp, vp, vp, vp, i32, i32, f32, u64, u64, vp, vp, vp, vp, vp],
+    "k3m_align_cosine_fwd": [vp, vp, i32, i32, f32, vp, vp, vp, vp],
 }
 
 _lib = None

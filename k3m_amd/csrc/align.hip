@@ -38,13 +38,14 @@ __global__ __launch_bounds__(NT) void pair_cat_bwd_kernel(const float* __restric
   }
 }
 
-// one workgroup per pair row: tanh, dropout, the two logits, softmax, CE row loss, dlogits, du
-__global__ __launch_bounds__(NT) void ce_rows_kernel(const float* __restrict__ u, const float* __restrict__ W,
-                                                     const float* __restrict__ bias, const float* __restrict__ labels,
-                                                     int B, int H, float p, uint64_t seed, uint64_t off,
-                                                     float* __restrict__ logits, float* __restrict__ probs,
-                                                     float* __restrict__ dlogits, float* __restrict__ loss_rows,
-                                                     float* __restrict__ du) {
+// one workgroup per pair row: tanh, dropout, the two logits, softmax, CE row loss, dlogits, du.  The one body of
+// ce_rows_kernel and ce_rows_fwd_kernel; GRAD = false: the forward-only form, no dlogits / du store
+template <bool GRAD>
+__device__ __forceinline__ void ce_rows_body(const float* __restrict__ u, const float* __restrict__ W,
+                                             const float* __restrict__ bias, const float* __restrict__ labels, int B,
+                                             int H, float p, uint64_t seed, uint64_t off, float* __restrict__ logits,
+                                             float* __restrict__ probs, float* __restrict__ dlogits,
+                                             float* __restrict__ loss_rows, float* __restrict__ du) {
   __shared__ float red[NW];
   const int b = blockIdx.x;
   const float* ub = u + (long long)b * H;
@@ -70,15 +71,36 @@ __global__ __launch_bounds__(NT) void ce_rows_kernel(const float* __restrict__ u
     logits[2 * b + 1] = l1;
     probs[2 * b] = p0;
     probs[2 * b + 1] = p1;
-    dlogits[2 * b] = d0;
-    dlogits[2 * b + 1] = d1;
+    if constexpr (GRAD) {
+      dlogits[2 * b] = d0;
+      dlogits[2 * b + 1] = d1;
+    }
     loss_rows[b] = ok ? lse - (y == 0 ? l0 : l1) : NAN;
   }
-  for (int c = threadIdx.x; c < H; c += NT) {
-    const float t = tanhf(ub[c]);
-    const float keep = k3m_dropout_scale(seed, off + (uint64_t)b * H + c, p);
-    du[(long long)b * H + c] = (d0 * W[c] + d1 * W[H + c]) * keep * (1.f - t * t);
+  if constexpr (GRAD) {
+    for (int c = threadIdx.x; c < H; c += NT) {
+      const float t = tanhf(ub[c]);
+      const float keep = k3m_dropout_scale(seed, off + (uint64_t)b * H + c, p);
+      du[(long long)b * H + c] = (d0 * W[c] + d1 * W[H + c]) * keep * (1.f - t * t);
+    }
   }
+}
+
+__global__ __launch_bounds__(NT) void ce_rows_kernel(const float* __restrict__ u, const float* __restrict__ W,
+                                                     const float* __restrict__ bias, const float* __restrict__ labels,
+                                                     int B, int H, float p, uint64_t seed, uint64_t off,
+                                                     float* __restrict__ logits, float* __restrict__ probs,
+                                                     float* __restrict__ dlogits, float* __restrict__ loss_rows,
+                                                     float* __restrict__ du) {
+  ce_rows_body<true>(u, W, bias, labels, B, H, p, seed, off, logits, probs, dlogits, loss_rows, du);
+}
+
+__global__ __launch_bounds__(NT) void ce_rows_fwd_kernel(const float* __restrict__ u, const float* __restrict__ W,
+                                                         const float* __restrict__ bias,
+                                                         const float* __restrict__ labels, int B, int H, float p,
+                                                         uint64_t seed, uint64_t off, float* __restrict__ logits,
+                                                         float* __restrict__ probs, float* __restrict__ loss_rows) {
+  ce_rows_body<false>(u, W, bias, labels, B, H, p, seed, off, logits, probs, nullptr, loss_rows, nullptr);
 }
 
 // out_proj weight/bias gradients (accumulated) and the mean loss; one thread per hidden column
@@ -112,9 +134,11 @@ __global__ __launch_bounds__(NT) void ce_reduce_kernel(const float* __restrict__
 
 // CosineEmbeddingLoss (ATen cosine_embedding_loss: EPSILON 1e-12 added to the squared norms) and
 // its gradient for both items; probs from cosine_similarity(e1, e1) (norms clamped at 1e-8)
-__global__ __launch_bounds__(NT) void cosine_rows_kernel(const float* __restrict__ e, const float* __restrict__ labels,
-                                                         int B, int H, float margin, float* __restrict__ probs,
-                                                         float* __restrict__ loss_rows, float* __restrict__ de) {
+// (the one body of cosine_rows_kernel and cosine_rows_fwd_kernel; GRAD = false: no de store)
+template <bool GRAD>
+__device__ __forceinline__ void cosine_rows_body(const float* __restrict__ e, const float* __restrict__ labels, int B,
+                                                 int H, float margin, float* __restrict__ probs,
+                                                 float* __restrict__ loss_rows, float* __restrict__ de) {
   __shared__ float red[NW];
   const int b = blockIdx.x;
   const float* x1 = e + (long long)b * H;
@@ -146,10 +170,25 @@ __global__ __launch_bounds__(NT) void cosine_rows_kernel(const float* __restrict
     loss_rows[b] = l;
     probs[b] = (s11 / (n1 * n1) + 1.f) * 0.5f;
   }
-  for (int c = threadIdx.x; c < H; c += NT) {
-    de[(long long)b * H + c] = dl * (x2[c] / denom - cs * x1[c] / m1);
-    de[(long long)(B + b) * H + c] = dl * (x1[c] / denom - cs * x2[c] / m2);
+  if constexpr (GRAD) {
+    for (int c = threadIdx.x; c < H; c += NT) {
+      de[(long long)b * H + c] = dl * (x2[c] / denom - cs * x1[c] / m1);
+      de[(long long)(B + b) * H + c] = dl * (x1[c] / denom - cs * x2[c] / m2);
+    }
   }
+}
+
+__global__ __launch_bounds__(NT) void cosine_rows_kernel(const float* __restrict__ e, const float* __restrict__ labels,
+                                                         int B, int H, float margin, float* __restrict__ probs,
+                                                         float* __restrict__ loss_rows, float* __restrict__ de) {
+  cosine_rows_body<true>(e, labels, B, H, margin, probs, loss_rows, de);
+}
+
+__global__ __launch_bounds__(NT) void cosine_rows_fwd_kernel(const float* __restrict__ e,
+                                                             const float* __restrict__ labels, int B, int H,
+                                                             float margin, float* __restrict__ probs,
+                                                             float* __restrict__ loss_rows) {
+  cosine_rows_body<false>(e, labels, B, H, margin, probs, loss_rows, nullptr);
 }
 
 __global__ void mean_kernel(const float* __restrict__ rows, int n, float* __restrict__ out) {
@@ -198,6 +237,31 @@ extern "C" int k3m_align_cosine_fwd_bwd(const float* e, const float* labels, int
                                         float* probs, float* loss_rows, float* de, hipStream_t st) {
   K3M_ARG(e && labels && loss && probs && loss_rows && de && B > 0 && H > 0);
   hipLaunchKernelGGL(cosine_rows_kernel, dim3(B), dim3(NT), 0, st, e, labels, B, H, margin, probs, loss_rows, de);
+  K3M_CHECK_LAUNCH();
+  hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(64), 0, st, loss_rows, B, loss);
+  K3M_CHECK_LAUNCH();
+  return 0;
+}
+
+// Forward-only forms of the two heads (prediction): the same row kernels' bodies without a gradient store, then the
+// mean of the row losses.
+extern "C" int k3m_align_ce_fwd(const float* u, const float* W, const float* bias, const float* labels, int B, int H,
+                                float p, uint64_t seed, uint64_t off, float* logits, float* probs, float* loss_rows,
+                                float* loss, hipStream_t st) {
+  K3M_ARG(u && W && bias && labels && logits && probs && loss_rows && loss);
+  K3M_ARG(B > 0 && H > 0 && p >= 0.f && p < 1.f);
+  hipLaunchKernelGGL(ce_rows_fwd_kernel, dim3(B), dim3(NT), 0, st, u, W, bias, labels, B, H, p, seed, off, logits,
+                     probs, loss_rows);
+  K3M_CHECK_LAUNCH();
+  hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(64), 0, st, loss_rows, B, loss);
+  K3M_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int k3m_align_cosine_fwd(const float* e, const float* labels, int B, int H, float margin, float* loss,
+                                    float* probs, float* loss_rows, hipStream_t st) {
+  K3M_ARG(e && labels && loss && probs && loss_rows && B > 0 && H > 0);
+  hipLaunchKernelGGL(cosine_rows_fwd_kernel, dim3(B), dim3(NT), 0, st, e, labels, B, H, margin, probs, loss_rows);
   K3M_CHECK_LAUNCH();
   hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(64), 0, st, loss_rows, B, loss);
   K3M_CHECK_LAUNCH();

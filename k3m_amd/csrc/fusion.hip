@@ -21,7 +21,9 @@ __global__ void relu_cat3_kernel(const T* x0, const T* x1, const T* x2, T* c, in
   }
 }
 
-template <typename T>
+// SAVE = false: the forward-only form (k3m_gate_fwd with ys == idx == NULL), no ys / idx store in the kernel; the
+// draws, the softmax arithmetic and the pick are the saving form's
+template <typename T, bool SAVE = true>
 __global__ void gate_fwd_kernel(const float* a, const T* c, const float* noise, float* ys, uint8_t* idx, T* out,
                                 int rows, int d, uint64_t seed, uint64_t off) {
   const long long n = (long long)rows * d;
@@ -49,10 +51,12 @@ __global__ void gate_fwd_kernel(const float* a, const T* c, const float* noise, 
     float best = y0;
     if (y1 > best) { best = y1; k = 1; }
     if (y2 > best) { k = 2; }
-    ys[b3] = y0;
-    ys[b3 + d] = y1;
-    ys[b3 + 2 * d] = y2;
-    idx[e] = (uint8_t)k;
+    if constexpr (SAVE) {
+      ys[b3] = y0;
+      ys[b3 + d] = y1;
+      ys[b3 + 2 * d] = y2;
+      idx[e] = (uint8_t)k;
+    }
     out[e] = c[b3 + k * d];
   }
 }
@@ -254,7 +258,7 @@ __global__ void relu_cat2_kernel(const T* x0, const T* x1, T* c, long long n4, i
   }
 }
 
-template <typename T>
+template <typename T, bool SAVE = true>   // SAVE as gate_fwd_kernel's
 __global__ void gate2_fwd_kernel(const float* a, const T* c, const float* noise, float* ys, uint8_t* idx, T* out,
                                  long long n4, int d4, uint64_t seed, uint64_t off) {
   const long long d = 4LL * d4;
@@ -289,9 +293,11 @@ __global__ void gate2_fwd_kernel(const float* a, const T* c, const float* noise,
       pick |= (one ? 1u : 0u) << (8 * k);
       o[k] = one ? c1[k] : c0[k];
     }
-    st4(ys + b2, y0);
-    st4(ys + b2 + d, y1);
-    *reinterpret_cast<uint32_t*>(idx + 4 * i) = pick;
+    if constexpr (SAVE) {
+      st4(ys + b2, y0);
+      st4(ys + b2 + d, y1);
+      *reinterpret_cast<uint32_t*>(idx + 4 * i) = pick;
+    }
     st4(out + 4 * i, o);
   }
 }
@@ -383,11 +389,17 @@ extern "C" int k3m_relu_cat3(const void* x0, const void* x1, const void* x2, voi
 
 extern "C" int k3m_gate_fwd(const float* a, const void* c, const float* noise, float* ys, uint8_t* idx, void* out,
                             int rows, int d, uint64_t seed, uint64_t off, int dtype, hipStream_t st) {
-  K3M_ARG(a && c && ys && idx && out);
+  K3M_ARG(a && c && out);
+  K3M_ARG((ys == nullptr) == (idx == nullptr));   // both saved, or the forward-only form
   const long long n = (long long)rows * d;
   if (n == 0) return 0;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(gate_fwd_kernel<T>, dim3(grid_for(n)), dim3(256), 0, st, a, (const T*)c, noise,
-                                       ys, idx, (T*)out, rows, d, seed, off));
+  if (ys) {
+    DISPATCH_T(dtype, hipLaunchKernelGGL(gate_fwd_kernel<T>, dim3(grid_for(n)), dim3(256), 0, st, a, (const T*)c,
+                                         noise, ys, idx, (T*)out, rows, d, seed, off));
+  } else {
+    DISPATCH_T(dtype, hipLaunchKernelGGL((gate_fwd_kernel<T, false>), dim3(grid_for(n)), dim3(256), 0, st, a,
+                                         (const T*)c, noise, ys, idx, (T*)out, rows, d, seed, off));
+  }
   K3M_CHECK_LAUNCH();
   return 0;
 }
@@ -427,13 +439,19 @@ extern "C" int k3m_relu_cat2(const void* x0, const void* x1, void* c, int rows, 
 
 extern "C" int k3m_gate2_fwd(const float* a, const void* c, const float* noise, float* ys, uint8_t* idx, void* out,
                              int rows, int d, uint64_t seed, uint64_t off, int dtype, hipStream_t st) {
-  K3M_ARG(a && c && ys && idx && out && rows >= 0 && d >= 0 && d % 4 == 0);
+  K3M_ARG(a && c && out && rows >= 0 && d >= 0 && d % 4 == 0);
+  K3M_ARG((ys == nullptr) == (idx == nullptr));   // both saved, or the forward-only form
   K3M_ARG(al4(a, K3M_F32) && al4(c, dtype) && al4(noise, K3M_F32) && al4(ys, K3M_F32) && al4(out, dtype) &&
           ((uintptr_t)idx & 3u) == 0);
   const long long n4 = (long long)rows * d / 4;
   if (n4 == 0) return 0;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(gate2_fwd_kernel<T>, dim3(grid_for(n4)), dim3(256), 0, st, a, (const T*)c,
-                                       noise, ys, idx, (T*)out, n4, d / 4, seed, off));
+  if (ys) {
+    DISPATCH_T(dtype, hipLaunchKernelGGL(gate2_fwd_kernel<T>, dim3(grid_for(n4)), dim3(256), 0, st, a, (const T*)c,
+                                         noise, ys, idx, (T*)out, n4, d / 4, seed, off));
+  } else {
+    DISPATCH_T(dtype, hipLaunchKernelGGL((gate2_fwd_kernel<T, false>), dim3(grid_for(n4)), dim3(256), 0, st, a,
+                                         (const T*)c, noise, ys, idx, (T*)out, n4, d / 4, seed, off));
+  }
   K3M_CHECK_LAUNCH();
   return 0;
 }

@@ -555,7 +555,10 @@ __global__ __launch_bounds__(256, NV <= 3 ? 2 : 1) void ln_bwd_bf16_kernel(const
 }
 
 // ------------------------------------------------------------------ embeddings
-template <typename T>
+// SAVE = false: the forward-only form (k3m_embed_fwd with xhat == rstd == NULL), no xhat / rstd store in the kernel.
+// Y1_T = false (T = float): the encoder copies y1 / y2 are bf16 rows (y0, the fusion's individual candidate, stays
+// fp32); from_f<bf16_t> rounds as k3m_convert does.
+template <typename T, bool SAVE = true, bool Y1_T = true>
 __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ tt,
                                                         const float* __restrict__ word, const float* __restrict__ pos,
                                                         const float* __restrict__ typ, const float* __restrict__ gamma,
@@ -588,22 +591,29 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restric
       sq += v[j][0] * v[j][0] + v[j][1] * v[j][1] + v[j][2] * v[j][2] + v[j][3] * v[j][3];
     }
   const float rs = 1.0f / sqrtf(wave_sum(sq) / cols + eps);
-  if (lane == 0) rstd[row] = rs;
+  if constexpr (SAVE) {
+    if (lane == 0) rstd[row] = rs;
+  }
   const long long base = (long long)row * cols;
 #pragma unroll
   for (int j = 0; j < MAXV; ++j)
     if (j < nv) {
       const int c = (lane + 64 * j) * 4;
       const floatx4 xh = v[j] * rs;
-      st4<T>(xhat + base + c, xh);
+      if constexpr (SAVE) st4<T>(xhat + base + c, xh);
       floatx4 o = *reinterpret_cast<const floatx4*>(gamma + c) * xh + *reinterpret_cast<const floatx4*>(beta + c);
       if (p_out > 0.f) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) o[q] *= k3m_dropout_scale(seed, off + base + c + q, p_out);
       }
       st4<T>(y0 + base + c, o);
-      if (y1) st4<T>(y1 + base + c, o);
-      if (y2) st4<T>(y2 + base + c, o);
+      if constexpr (Y1_T) {
+        if (y1) st4<T>(y1 + base + c, o);
+        if (y2) st4<T>(y2 + base + c, o);
+      } else {
+        if (y1) st4<bf16_t>(reinterpret_cast<bf16_t*>(y1) + base + c, o);
+        if (y2) st4<bf16_t>(reinterpret_cast<bf16_t*>(y2) + base + c, o);
+      }
     }
 }
 
@@ -1007,19 +1017,39 @@ extern "C" int k3m_ln_bwd(const void* dy, const void* xhat, const float* rstd, c
   return k3m_slab_reduce_batch(wsa, outs, ns, cs, acc, dxsum ? 3 : 2, st);
 }
 
+extern "C" int k3m_embed_fwd_ex(const int64_t* ids, const int64_t* tt, const float* word, const float* pos,
+                                const float* type, const float* gamma, const float* beta, void* y0, void* y1, void* y2,
+                                void* xhat, float* rstd, int nseq, int len, int hidden, float eps, float p_out,
+                                uint64_t seed, uint64_t off, int dtype, int y1_dtype, hipStream_t st) {
+  K3M_ARG(ids && tt && word && pos && type && gamma && beta && y0);
+  K3M_ARG((xhat == nullptr) == (rstd == nullptr));   // both saved, or the forward-only form
+  K3M_ARG(hidden % 256 == 0 && hidden <= 1024 && hidden > 0 && nseq >= 0 && len >= 0);
+  K3M_ARG(y1_dtype == dtype || (dtype == K3M_F32 && y1_dtype == K3M_BF16 && !xhat));
+  const int rows = nseq * len;
+  if (rows == 0) return 0;
+  if (xhat) {
+    DISPATCH_T(dtype, hipLaunchKernelGGL(embed_fwd_kernel<T>, dim3(k3m_cdiv(rows, 4)), dim3(256), 0, st, ids, tt, word,
+                                         pos, type, gamma, beta, (T*)y0, (T*)y1, (T*)y2, (T*)xhat, rstd, rows, len,
+                                         hidden, eps, p_out, seed, off));
+  } else if (y1_dtype != dtype) {
+    hipLaunchKernelGGL((embed_fwd_kernel<float, false, false>), dim3(k3m_cdiv(rows, 4)), dim3(256), 0, st, ids, tt,
+                       word, pos, type, gamma, beta, (float*)y0, (float*)y1, (float*)y2, (float*)nullptr, rstd, rows,
+                       len, hidden, eps, p_out, seed, off);
+  } else {
+    DISPATCH_T(dtype, hipLaunchKernelGGL((embed_fwd_kernel<T, false>), dim3(k3m_cdiv(rows, 4)), dim3(256), 0, st, ids,
+                                         tt, word, pos, type, gamma, beta, (T*)y0, (T*)y1, (T*)y2, (T*)xhat, rstd, rows,
+                                         len, hidden, eps, p_out, seed, off));
+  }
+  K3M_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int k3m_embed_fwd(const int64_t* ids, const int64_t* tt, const float* word, const float* pos,
                              const float* type, const float* gamma, const float* beta, void* y0, void* y1, void* y2,
                              void* xhat, float* rstd, int nseq, int len, int hidden, float eps, float p_out,
                              uint64_t seed, uint64_t off, int dtype, hipStream_t st) {
-  K3M_ARG(ids && tt && word && pos && type && gamma && beta && y0 && xhat && rstd);
-  K3M_ARG(hidden % 256 == 0 && hidden <= 1024);
-  const int rows = nseq * len;
-  if (rows == 0) return 0;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(embed_fwd_kernel<T>, dim3(k3m_cdiv(rows, 4)), dim3(256), 0, st, ids, tt, word,
-                                       pos, type, gamma, beta, (T*)y0, (T*)y1, (T*)y2, (T*)xhat, rstd, rows, len,
-                                       hidden, eps, p_out, seed, off));
-  K3M_CHECK_LAUNCH();
-  return 0;
+  return k3m_embed_fwd_ex(ids, tt, word, pos, type, gamma, beta, y0, y1, y2, xhat, rstd, nseq, len, hidden, eps, p_out,
+                          seed, off, dtype, dtype, st);
 }
 
 extern "C" int k3m_embed_bwd(const int64_t* ids, const int64_t* tt, const void* ds, float* dword, float* dpos,

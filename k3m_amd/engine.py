@@ -286,7 +286,6 @@ class BertLayerOp(object):
         """-> (y, saved).  save=False (a layer below the fixed_t_layer cut): the same values and rng.take sequence
         from the forward-only kernel forms (no GELU pre-activation, xhat / rstd, probabilities / LSE); the saved
         tuple then holds None in their places."""
-        assert save or self.dyn is None
         M, H = x.shape
         qkv = self.qkv.fwd(x)
         dsv = self.dyn.gate(partner) if self.dyn is not None else None
@@ -369,32 +368,33 @@ class ConnectionOp(object):
 
     # Cut into segments at the GEMM stages like BertLayerOp: the three co-attention blocks of one schedule step
     # issue their (independent) GEMMs together and each stage runs as one grouped launch (_lockstep).
-    def fwd_steps(self, s1, s2, nseq, l1, l2, mask1, mask2, rng, out1, out2):
-        """-> saved; the outputs land in out1 / out2"""
+    def fwd_steps(self, s1, s2, nseq, l1, l2, mask1, mask2, rng, out1, out2, save=True):
+        """-> saved; the outputs land in out1 / out2.  save=False: the forward-only kernel forms, as
+        BertLayerOp.fwd_steps; s1 / s2 may then alias rows another block of the same lock step reads."""
         Hb = self.qkv1.W.shape[0] // 3
         q1 = self.qkv1.fwd(s1)
         q2 = self.qkv2.fwd(s2)
         yield
         # ctx1: stream-2 queries over stream-1 keys (+ stream-1 mask); ctx2 the converse (:786-824)
         ctx1, a1s = ops.branch(_attn_fwd, q2[:, 0:Hb], q1[:, Hb:2 * Hb], q1[:, 2 * Hb:], mask1, nseq, l2, l1, self.nh,
-                               self.pa1, rng)
+                               self.pa1, rng, save=save)
         ctx2, a2s = ops.branch(_attn_fwd, q1[:, 0:Hb], q2[:, Hb:2 * Hb], q2[:, 2 * Hb:], mask2, nseq, l1, l2, self.nh,
-                               self.pa2, rng)
+                               self.pa2, rng, save=save)
         x1 = self.d1.fwd(ctx2)
         x2 = self.d2.fwd(ctx1)
         yield
-        h1, t1s = self.t1.fwd(x1, s1, rng)
-        h2, t2s = self.t2.fwd(x2, s2, rng)
-        u1 = torch.empty((h1.shape[0], self.f1.i.W.shape[0]), dtype=h1.dtype, device=h1.device)
-        u2 = torch.empty((h2.shape[0], self.f2.i.W.shape[0]), dtype=h2.dtype, device=h2.device)
+        h1, t1s = self.t1.fwd(x1, s1, rng, save=save)
+        h2, t2s = self.t2.fwd(x2, s2, rng, save=save)
+        u1 = torch.empty((h1.shape[0], self.f1.i.W.shape[0]), dtype=h1.dtype, device=h1.device) if save else None
+        u2 = torch.empty((h2.shape[0], self.f2.i.W.shape[0]), dtype=h2.dtype, device=h2.device) if save else None
         g1 = self.f1.i.fwd(h1, epi=L.EPI_BIAS_GELU, aux=u1)
         g2 = self.f2.i.fwd(h2, epi=L.EPI_BIAS_GELU, aux=u2)
         yield
         o1 = self.f1.o.fwd(g1)
         o2 = self.f2.o.fwd(g2)
         yield
-        _, ts1 = self.f1.tail.fwd(o1, h1, rng, out=out1)
-        _, ts2 = self.f2.tail.fwd(o2, h2, rng, out=out2)
+        _, ts1 = self.f1.tail.fwd(o1, h1, rng, out=out1, save=save)
+        _, ts2 = self.f2.tail.fwd(o2, h2, rng, out=out2, save=save)
         return (s1, s2, q1, q2, ctx1, ctx2, a1s, a2s, t1s, t2s, (h1, u1, g1, ts1), (h2, u2, g2, ts2), Hb)
 
     def bwd_steps(self, dy1, dy2, saved, ds1, ds2):
@@ -530,6 +530,21 @@ def validate_config(cfg):
     # without the connection blocks (vilbert_k3m.py:1143-1152, :1275, :1453, :1629): accepted
 
 
+def schedule(cfg):
+    """K3MEngine._schedule as a function of the config alone (with the 'v' entries; no device)."""
+    sch = []
+    t0 = v0 = 0
+    for i, (v1, t1) in enumerate(zip(cfg.v_biattention_id, cfg.t_biattention_id)):
+        sch += [("t", k) for k in range(t0, t1)]
+        sch += [("v", k) for k in range(v0, v1)]
+        if cfg.with_coattention:
+            sch.append(("c", i))
+        t0, v0 = t1, v1
+    sch += [("v", k) for k in range(v0, cfg.v_num_hidden_layers)]
+    sch += [("t", k) for k in range(t0, cfg.num_hidden_layers)]
+    return sch
+
+
 class K3MEngine(object):
     """One replica of the model on one GPU (one process per GPU; DDP in k3m_amd/ddp.py)."""
 
@@ -563,6 +578,9 @@ class K3MEngine(object):
         # saving kernels for them (A/B knob: the cost of the saves alone)
         self.fixed_t = int(getattr(c, "fixed_t_layer", 0))
         self.frozen_nosave = os.environ.get("K3M_FROZEN_NOSAVE", "1") != "0"
+        # embed(): identical copies of a stream stay one buffer until they diverge (k3m_amd/infer.py infer_plan).
+        # K3M_INFER_DEDUP=0 keeps the wide buffers from the start (A/B knob: the launches of forward(train=False))
+        self.infer_dedup = os.environ.get("K3M_INFER_DEDUP", "1") != "0"
         # the tensors that are never-grad because of the cut alone (the module surface leaves their .grad None)
         self.cut_frozen = fp.frozen - {n for n, _ in fp.spec if is_frozen(n, _without_cut(c))} if self.fixed_t else set()
         # False: no connection blocks (the reference registers none, vilbert_k3m.py:1143-1152): the schedule has no
@@ -634,18 +652,7 @@ class K3MEngine(object):
         ('c', i) entries are left out and the t / v order stays the reference loop's (vilbert_k3m.py:1185-1290): in
         iteration i the text layers below t_biattention_id[i], then the image layers below v_biattention_id[i]
         (observable with dynamic attention, where an image layer reads the text state)."""
-        c = self.cfg
-        sch = []
-        t0 = v0 = 0
-        for i, (v1, t1) in enumerate(zip(c.v_biattention_id, c.t_biattention_id)):
-            sch += [("t", k) for k in range(t0, t1)]
-            sch += [("v", k) for k in range(v0, v1)]
-            if self.coattn:
-                sch.append(("c", i))
-            t0, v0 = t1, v1
-        sch += [("v", k) for k in range(v0, c.v_num_hidden_layers)]
-        sch += [("t", k) for k in range(t0, c.num_hidden_layers)]
-        return sch
+        return schedule(self.cfg)
 
     def _below_cut(self, kind, i):
         return kind == "t" and i < self.fixed_t
@@ -680,9 +687,10 @@ class K3MEngine(object):
                                    "collation, or a hand-built _label_counts)" % (hint, got))
 
     # ------------------------------------------------------------ stages of both steps (this one and engine_text's)
-    def _struct_fwd(self, ctx, batch, seq_tp, c_init, rng, ent_neg, val_neg, groups):
+    def _struct_fwd(self, ctx, batch, seq_tp, c_init, rng, ent_neg, val_neg, groups, save=True):
         """Structure aggregator + LPM (:2413-2505) over the PV rows of seq_tp; returns (c_final, LPM loss), the loss
-        None for a task other than pretraining (the encoder up to c_final only)."""
+        None for a task other than pretraining (the encoder up to c_final only).  save=False (embed): the
+        aggregator alone for every task; ctx (B, T, P) is only read."""
         c, fp, dev = self.cfg, self.fp, self.device
         B, T, P, H = ctx["B"], ctx["T"], ctx["P"], self.H
         BT = B * T
@@ -708,6 +716,8 @@ class K3MEngine(object):
                    att[r0:].data_ptr(), agg[r0:].data_ptr(), Bg, NPV, H, L.stream())
         c_final = c_init.clone()
         self.sw3.fwd(agg, out=c_final, beta=1.0)
+        if not save:
+            return c_final, None
         ctx["groups"] = groups
         ctx["batch"] = batch
         if self.task != "pretrain":
@@ -864,6 +874,67 @@ class K3MEngine(object):
                L.stream())
         return dci
 
+    def _fusion_fwd(self, streams, noise, rng, save=True):
+        """Initial-interactive fusion (get_sequence_pooled_output_final :2376-2411) of streams {m: (individual,
+        cross 1, cross 2, out, width)}; returns (what the backward keeps per modality, the fusion mode).
+        save=False: the hard gate's forward-only kernel form (no ys / idx; the same draws)."""
+        c, dev = self.cfg, self.device
+        mode = getattr(c, "if_pre_sampling", 1)
+        fus = {}
+        gate_a = {}
+        if mode not in (0, 1, 2, 3):
+            raise NotImplementedError("if_pre_sampling=%s" % mode)
+        if mode in (1, 2):   # the three modalities' gate GEMMs are independent: one grouped launch (GROUP_GATE)
+            ccs = {}
+            for m in ("v", "t", "pv"):
+                x0, x1, x2, out, D = streams[m]
+                rows = x0.shape[0]
+                cc = torch.empty((rows, 3 * D), dtype=torch.float32, device=dev)
+                L.call("k3m_relu_cat3", x0.data_ptr(), x1.data_ptr(), x2.data_ptr(), cc.data_ptr(), rows, D, L.F32,
+                       L.stream())
+                ccs[m] = (cc, self._lo(cc))
+            with (ops.grouped() if GROUP_GATE else contextlib.nullcontext()):
+                for m in ("v", "t", "pv"):
+                    gate_a[m] = self.gate[m].fwd(ccs[m][1], epi=L.EPI_BIAS_SIGMOID, out_dtype=torch.float32)
+        if mode == 2:
+            # soft gate (:2300-2329): out = soft_m(c * sigmoid(scores)), no gumbel draw.  z is written in the
+            # soft GEMMs' operand dtype (bf16 directly in bf16 mode); the three GEMMs are one grouped launch.
+            for m in ("v", "t", "pv"):
+                cc, cclo = ccs[m]
+                rows, D = streams[m][0].shape[0], streams[m][4]
+                z = torch.empty((rows, 3 * D), dtype=cclo.dtype, device=dev)
+                L.call("k3m_soft_scale", cc.data_ptr(), gate_a[m].data_ptr(), z.data_ptr(), rows, D, L.F32,
+                       ops.dt(z), L.stream())
+                fus[m] = (cc, gate_a[m], z, cclo)
+            with (ops.grouped() if GROUP_GATE else contextlib.nullcontext()):
+                for m in ("v", "t", "pv"):
+                    self.soft[m].fwd(fus[m][2], out=streams[m][3])
+        for m in (() if mode == 2 else ("v", "t", "pv")):
+            x0, x1, x2, out, D = streams[m]
+            rows = x0.shape[0]
+            if mode == 1:
+                cc = ccs[m][0]
+                a = gate_a[m]
+                ys = torch.empty_like(a) if save else None
+                idx = torch.empty((rows * D,), dtype=torch.uint8, device=dev) if save else None
+                nz = None
+                off_g = 0
+                if noise is not None:
+                    nz = noise[m].reshape(rows * 3 * D).to(device=dev, dtype=torch.float32).contiguous()
+                else:
+                    off_g = rng.take(rows * 3 * D)
+                L.call("k3m_gate_fwd", a.data_ptr(), cc.data_ptr(), L.ptr(nz), L.ptr(ys), L.ptr(idx),
+                       out.data_ptr(), rows, D, rng.seed, off_g, L.F32, L.stream())
+                fus[m] = (cc, a, ys, idx)
+            elif mode == 0:
+                L.call("k3m_mean3", x0.data_ptr(), x1.data_ptr(), x2.data_ptr(), out.data_ptr(), out.numel(), L.F32,
+                       L.stream())
+                fus[m] = None
+            else:   # 3, interactive only (:2388-2402): the individual stream does not enter the fusion
+                L.call("k3m_mean2", x1.data_ptr(), x2.data_ptr(), out.data_ptr(), out.numel(), L.F32, L.stream())
+                fus[m] = None
+        return fus, mode
+
     def forward(self, batch, train=True, noise=None, ent_neg=None, val_neg=None, seed=None, groups=1):
         """Runs the forward of the step; returns (losses dict of device tensors, ctx for backward).
 
@@ -1004,7 +1075,6 @@ class K3MEngine(object):
         ctx["XT"], ctx["XV"] = XT, XV
 
         # ---- initial-interactive fusion (get_sequence_pooled_output_final :2376-2411)
-        mode = getattr(c, "if_pre_sampling", 1)
         seq_tp = torch.empty((BT + BP, H), dtype=torch.float32, device=dev)
         seq_v = torch.empty((BR, Hv), dtype=torch.float32, device=dev)
         streams = {
@@ -1012,59 +1082,7 @@ class K3MEngine(object):
             "t": (ind_t, XT[0:BT], XT[BT:2 * BT], seq_tp[0:BT], H),
             "pv": (ind_pv, XT[2 * BT:2 * BT + BP], XT[2 * BT + BP:], seq_tp[BT:], H),
         }
-        fus = {}
-        gate_a = {}
-        if mode not in (0, 1, 2, 3):
-            raise NotImplementedError("if_pre_sampling=%s" % mode)
-        if mode in (1, 2):   # the three modalities' gate GEMMs are independent: one grouped launch (GROUP_GATE)
-            ccs = {}
-            for m in ("v", "t", "pv"):
-                x0, x1, x2, out, D = streams[m]
-                rows = x0.shape[0]
-                cc = torch.empty((rows, 3 * D), dtype=torch.float32, device=dev)
-                L.call("k3m_relu_cat3", x0.data_ptr(), x1.data_ptr(), x2.data_ptr(), cc.data_ptr(), rows, D, L.F32,
-                       L.stream())
-                ccs[m] = (cc, self._lo(cc))
-            with (ops.grouped() if GROUP_GATE else contextlib.nullcontext()):
-                for m in ("v", "t", "pv"):
-                    gate_a[m] = self.gate[m].fwd(ccs[m][1], epi=L.EPI_BIAS_SIGMOID, out_dtype=torch.float32)
-        if mode == 2:
-            # soft gate (:2300-2329): out = soft_m(c * sigmoid(scores)), no gumbel draw.  z is written in the
-            # soft GEMMs' operand dtype (bf16 directly in bf16 mode); the three GEMMs are one grouped launch.
-            for m in ("v", "t", "pv"):
-                cc, cclo = ccs[m]
-                rows, D = streams[m][0].shape[0], streams[m][4]
-                z = torch.empty((rows, 3 * D), dtype=cclo.dtype, device=dev)
-                L.call("k3m_soft_scale", cc.data_ptr(), gate_a[m].data_ptr(), z.data_ptr(), rows, D, L.F32,
-                       ops.dt(z), L.stream())
-                fus[m] = (cc, gate_a[m], z, cclo)
-            with (ops.grouped() if GROUP_GATE else contextlib.nullcontext()):
-                for m in ("v", "t", "pv"):
-                    self.soft[m].fwd(fus[m][2], out=streams[m][3])
-        for m in (() if mode == 2 else ("v", "t", "pv")):
-            x0, x1, x2, out, D = streams[m]
-            rows = x0.shape[0]
-            if mode == 1:
-                cc = ccs[m][0]
-                a = gate_a[m]
-                ys = torch.empty_like(a)
-                idx = torch.empty((rows * D,), dtype=torch.uint8, device=dev)
-                nz = None
-                off_g = 0
-                if noise is not None:
-                    nz = noise[m].reshape(rows * 3 * D).to(device=dev, dtype=torch.float32).contiguous()
-                else:
-                    off_g = rng.take(rows * 3 * D)
-                L.call("k3m_gate_fwd", a.data_ptr(), cc.data_ptr(), L.ptr(nz), ys.data_ptr(), idx.data_ptr(),
-                       out.data_ptr(), rows, D, rng.seed, off_g, L.F32, L.stream())
-                fus[m] = (cc, a, ys, idx)
-            elif mode == 0:
-                L.call("k3m_mean3", x0.data_ptr(), x1.data_ptr(), x2.data_ptr(), out.data_ptr(), out.numel(), L.F32,
-                       L.stream())
-                fus[m] = None
-            else:   # 3, interactive only (:2388-2402): the individual stream does not enter the fusion
-                L.call("k3m_mean2", x1.data_ptr(), x2.data_ptr(), out.data_ptr(), out.numel(), L.F32, L.stream())
-                fus[m] = None
+        fus, mode = self._fusion_fwd(streams, noise, rng)
         ctx["fus"] = (fus, streams, mode)
         ctx["seq_tp"], ctx["seq_v"] = seq_tp, seq_v
 
@@ -1152,6 +1170,15 @@ class K3MEngine(object):
         out["loss"] = losses[0:1] + losses[1:2] + losses[2:3] + lpm
         out.update(captured)
         return out, ctx
+
+    def embed(self, batch, noise=None, seed=None, groups=1):
+        """Item-embedding inference (K3MForItemAlignment.item_embedding, vilbert_k3m.py:3329-3377): the forward up
+        to c_final in eval mode through the forward-only kernel forms.  Returns {c_initial, c_final, pooled_t,
+        pooled_pv, pooled_v} and no ctx: nothing is kept for a backward.  Every dropout is off; the hard gate's
+        gumbel draw stays (the reference draws it in eval mode too), reproducible by ``seed`` or explicit through
+        ``noise``.  Works for both tasks (no head, no LPM, no label field read).  k3m_amd/infer.py."""
+        from . import infer
+        return infer.embed(self, batch, noise=noise, seed=seed, groups=groups)
 
     # ------------------------------------------------------------ backward
     def backward(self, ctx, w_mlm=1.0, w_img=1.0, w_lpm=1.0, grad_ready=None, w_mlm_pv=None):

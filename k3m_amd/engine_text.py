@@ -25,6 +25,31 @@ from . import engine as E
 from . import ops
 
 
+def gate_fwd(eng, ind, XT, seq_tp, noise, rng, BT, BP, save=True):
+    """The two-candidate hard gate over [individual | cross] of the [title | PV] rows into seq_tp; returns what the
+    backward keeps.  save=False: the forward-only kernel form (no ys / idx; the same draws)."""
+    dev, H = eng.device, eng.H
+    Nt = BT + BP
+    f32 = dict(dtype=torch.float32, device=dev)
+    cc = torch.empty((Nt, 2 * H), **f32)
+    L.call("k3m_relu_cat2", ind.data_ptr(), XT.data_ptr(), cc.data_ptr(), Nt, H, L.F32, L.stream())
+    cclo = eng._lo(cc)
+    a = torch.empty((Nt, 2 * H), **f32)
+    with (ops.grouped() if E.GROUP_GATE else contextlib.nullcontext()):
+        eng.gate["t"].fwd(cclo[0:BT], out=a[0:BT], epi=L.EPI_BIAS_SIGMOID)
+        eng.gate["pv"].fwd(cclo[BT:], out=a[BT:], epi=L.EPI_BIAS_SIGMOID)
+    ys = torch.empty_like(a) if save else None
+    idx = torch.empty((Nt * H,), dtype=torch.uint8, device=dev) if save else None
+    nz, off_g = None, 0
+    if noise is not None:
+        nz = torch.cat([noise["t"].reshape(BT, 2 * H), noise["pv"].reshape(BP, 2 * H)]).to(**f32).contiguous()
+    else:
+        off_g = rng.take(Nt * 2 * H)
+    L.call("k3m_gate2_fwd", a.data_ptr(), cc.data_ptr(), L.ptr(nz), L.ptr(ys), L.ptr(idx), seq_tp.data_ptr(),
+           Nt, H, rng.seed, off_g, L.F32, L.stream())
+    return (cc, a, ys, idx)
+
+
 def forward(eng, batch, train=True, noise=None, ent_neg=None, val_neg=None, seed=None, groups=1):
     """K3MEngine.forward for use_image=False.  noise: optional {t: [B,T,2,H], pv: [B,P,2,H]}.  The image
     fields of ``batch`` (image_feat, image_loc, image_mask, image_label, image_target) are not read."""
@@ -83,24 +108,8 @@ def forward(eng, batch, train=True, noise=None, ent_neg=None, val_neg=None, seed
         XT = ops.convert(XT, torch.empty((Nt, H), **f32))
 
     # ---- two-candidate hard gate over [individual | cross]
-    cc = torch.empty((Nt, 2 * H), **f32)
-    L.call("k3m_relu_cat2", ind.data_ptr(), XT.data_ptr(), cc.data_ptr(), Nt, H, L.F32, L.stream())
-    cclo = eng._lo(cc)
-    a = torch.empty((Nt, 2 * H), **f32)
-    with (ops.grouped() if E.GROUP_GATE else contextlib.nullcontext()):
-        eng.gate["t"].fwd(cclo[0:BT], out=a[0:BT], epi=L.EPI_BIAS_SIGMOID)
-        eng.gate["pv"].fwd(cclo[BT:], out=a[BT:], epi=L.EPI_BIAS_SIGMOID)
-    ys = torch.empty_like(a)
-    idx = torch.empty((Nt * H,), dtype=torch.uint8, device=dev)
     seq_tp = torch.empty((Nt, H), **f32)
-    nz, off_g = None, 0
-    if noise is not None:
-        nz = torch.cat([noise["t"].reshape(BT, 2 * H), noise["pv"].reshape(BP, 2 * H)]).to(**f32).contiguous()
-    else:
-        off_g = rng.take(Nt * 2 * H)
-    L.call("k3m_gate2_fwd", a.data_ptr(), cc.data_ptr(), L.ptr(nz), ys.data_ptr(), idx.data_ptr(), seq_tp.data_ptr(),
-           Nt, H, rng.seed, off_g, L.F32, L.stream())
-    ctx["fus"] = (cc, a, ys, idx)
+    ctx["fus"] = gate_fwd(eng, ind, XT, seq_tp, noise, rng, BT, BP)
     ctx["seq_tp"] = seq_tp
 
     # ---- pooled outputs and c_initial (:2408-2409, :2725)

@@ -80,22 +80,81 @@ class K3MForItemAlignment(object):
     def __call__(self, *args, **kw):
         return self.forward(*args, **kw)
 
-    def forward(self, *args, output_all_attention_masks=False, train=True, noise=None, seed=None, **kw):
-        """Positional / keyword arguments as K3MForItemAlignment.forward.  noise: optional pair
-        (noise_item1, noise_item2) of {v,t,pv} gumbel-noise dicts (explicit randomness for parity).
-        With cfg.use_image false the image arguments may be None or left out ({t,pv} noise of 2 candidates)."""
+    def _stacked(self, args, kw, noise):
+        """forward's / predict's arguments -> (pair dict, the engine's stacked 2B batch, stacked noise, B)"""
         pair = dict(zip(ARG_NAMES, args))
         pair.update({k: v for k, v in kw.items() if k in ARG_NAMES})
         eng = self.engine
         missing = [k for k in ARG_NAMES if k not in pair and (eng.use_image or not _is_image_arg(k))]
         if missing:
             raise TypeError("missing arguments: %s" % missing)
-        dev = eng.device
-        batch = stack_pair(pair, dev, eng.use_image)
-        B = pair["input_ids_1"].shape[0]
+        batch = stack_pair(pair, eng.device, eng.use_image)
         nz = None
         if noise is not None:
             nz = {k: torch.cat([noise[0][k], noise[1][k]]) for k in noise[0]}
+        return pair, batch, nz, pair["input_ids_1"].shape[0]
+
+    def item_embedding(self, input_ids, image_feat=None, image_loc=None, token_type_ids=None, attention_mask=None,
+                       image_attention_mask=None, output_all_attention_masks=False, input_ids_pv=None,
+                       token_type_ids_pv=None, attention_mask_pv=None, index_p=None, index_v=None, noise=None,
+                       seed=None):
+        """K3MForItemAlignment.item_embedding (vilbert_k3m.py:3329-3377): (c_initial, c_final) of a batch of items
+        through engine.embed (forward-only kernels, nothing kept for a backward).  The image arguments may be None
+        without the image modality.  noise: optional {v,t,pv} gumbel-noise dict; seed: the draw's seed otherwise."""
+        eng = self.engine
+        given = {"input_ids": input_ids, "token_type_ids": token_type_ids, "attention_mask": attention_mask,
+                 "input_ids_pv": input_ids_pv, "token_type_ids_pv": token_type_ids_pv,
+                 "attention_mask_pv": attention_mask_pv, "index_p": index_p, "index_v": index_v,
+                 "image_feat": image_feat, "image_loc": image_loc, "image_attention_mask": image_attention_mask}
+        batch = {}
+        for src, dst in _ENGINE_NAMES:
+            if not eng.use_image and _is_image_arg(src):
+                continue
+            if given[src] is None:
+                raise TypeError("missing argument: %s" % src)
+            batch[dst] = given[src].to(eng.device).contiguous()
+        out = eng.embed(batch, noise=noise, seed=seed)
+        return out["c_initial"], out["c_final"]
+
+    def predict(self, *args, output_all_attention_masks=False, noise=None, seed=None, embeddings=False, **kw):
+        """forward's arguments and 4-tuple in eval mode, through engine.embed(groups=2) and the forward-only pair
+        head.  No ctx is made and no gradient buffer is touched; a pending forward()'s ctx is left as it is, so
+        forward, predict, backward runs the backward of that forward.  seed: the hard gate's draw when no noise is
+        given (None: the engine's step count).  embeddings=True: the first two results are c_final of the two items
+        for every loss type (for "ce" the reference returns the two class probabilities there)."""
+        pair, batch, nz, B = self._stacked(args, kw, noise)
+        eng = self.engine
+        dev, fp = eng.device, eng.fp
+        cf = eng.embed(batch, noise=nz, seed=seed, groups=2)["c_final"]
+        H = cf.shape[1]
+        labels = pair["labels"].to(device=dev, dtype=torch.float32).contiguous()
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        rows = torch.empty((B,), dtype=torch.float32, device=dev)
+        if self.loss_type == "ce":
+            x = torch.empty((B, 2 * H), dtype=torch.float32, device=dev)
+            L.call("k3m_align_pair_cat", cf.data_ptr(), B, H, 0.0, 0, HEAD_OFFSET, x.data_ptr(), L.stream())
+            u = self.cls_dense.fwd(x)
+            logits = torch.empty((B, 2), dtype=torch.float32, device=dev)
+            probs = torch.empty_like(logits)
+            L.call("k3m_align_ce_fwd", u.data_ptr(), fp.p["classifier.out_proj.weight"].data_ptr(),
+                   fp.p["classifier.out_proj.bias"].data_ptr(), labels.data_ptr(), B, H, 0.0, 0,
+                   HEAD_OFFSET + 2 * B * H, logits.data_ptr(), probs.data_ptr(), rows.data_ptr(), loss.data_ptr(),
+                   L.stream())
+            if embeddings:
+                return (cf[:B], cf[B:], probs[:, 1], loss)
+            return (probs[:, 0], probs[:, 1], probs[:, 1], loss)
+        probs = torch.empty((B,), dtype=torch.float32, device=dev)
+        L.call("k3m_align_cosine_fwd", cf.data_ptr(), labels.data_ptr(), B, H, 0.0, loss.data_ptr(), probs.data_ptr(),
+               rows.data_ptr(), L.stream())
+        return (cf[:B], cf[B:], probs, loss)
+
+    def forward(self, *args, output_all_attention_masks=False, train=True, noise=None, seed=None, **kw):
+        """Positional / keyword arguments as K3MForItemAlignment.forward.  noise: optional pair
+        (noise_item1, noise_item2) of {v,t,pv} gumbel-noise dicts (explicit randomness for parity).
+        With cfg.use_image false the image arguments may be None or left out ({t,pv} noise of 2 candidates)."""
+        pair, batch, nz, B = self._stacked(args, kw, noise)
+        eng = self.engine
+        dev = eng.device
         out, ctx = eng.forward(batch, train=train, noise=nz, seed=seed, groups=2)
         cf = out["c_final"]
         H = cf.shape[1]
@@ -184,20 +243,24 @@ class ItemAlignmentTrainer(Trainer):
         return {"item_embedding_1": e1, "item_embedding_2": e2, "probs": probs, "loss": loss}
 
 
-def evaluate(model, batches, thresholds=None):
+def evaluate(model, batches, thresholds=None, forward_only=False):
     """finetune.py:519-617 evaluation: the pair model in eval mode over ``batches`` (dicts with the
     forward's argument names), probs collected on the host, precision / recall / F1 of
     ``probs >= threshold`` for thresholds 0.1 .. 0.9.  (The reference concatenates with
     ``np.concatenate(model_probs, probs)`` — the second argument is the axis, so it fails from the
-    second batch on; here the batches are concatenated.)"""
+    second batch on; here the batches are concatenated.)  forward_only: through predict() (engine.embed: nothing
+    saved for a backward), the hard gate's draw seeded by the batch index."""
     import numpy as np
     from sklearn.metrics import f1_score, precision_score, recall_score
     if thresholds is None:
         thresholds = np.arange(0.1, 1.0, 0.1)
     probs, labels = [], []
-    for pair in batches:
-        _, _, p, _ = model.forward(**_pair_args(pair, model.engine.use_image), train=False)
-        model._ctx = None   # no backward in evaluation
+    for bi, pair in enumerate(batches):
+        if forward_only:
+            _, _, p, _ = model.predict(**_pair_args(pair, model.engine.use_image), seed=bi)
+        else:
+            _, _, p, _ = model.forward(**_pair_args(pair, model.engine.use_image), train=False)
+            model._ctx = None   # no backward in evaluation
         probs.append(p.detach().float().cpu().numpy())
         labels.append(pair["labels"].detach().float().cpu().numpy())
     probs = np.concatenate(probs) if probs else np.zeros(0)
@@ -216,3 +279,33 @@ def save_model(model, path):
     """The per-epoch ``K3M_item_alignment-<p>_epoch-<e>.bin`` (finetune.py:618-621): state_dict()."""
     from .checkpoint import model_state_dict
     torch.save(model_state_dict(model.engine.fp), path)
+
+
+def _emb_field(v):
+    """The reference's string layout of an embedding field (finetune.py:1202-1203): "[a,b,...]" of str(np.float32)
+    for a vector, "[x]" for a scalar (the ce head's probabilities)."""
+    import numpy as np
+    return "[%s]" % (",".join(str(x) for x in v) if isinstance(v, np.ndarray) else str(v))
+
+
+def write_predictions(model, batches, path, threshold, output="reference", noise=None, seed=0):
+    """The prediction loop of finetune.py:1119-1207: one .jsonl line per pair with the reference's keys and string
+    layout.  batches: pair dicts with the forward's argument names plus "item_ids_1" / "item_ids_2" (lists of item
+    ids).  output="reference": the forward's two "embeddings" (for ce, probs[:, 0] and probs[:, 1], as upstream);
+    output="embedding": c_final of both items for every loss type.  noise: optional per-batch list of noise pairs;
+    without it batch b draws the hard gate's noise with seed + b, so the file is reproducible from the call."""
+    import json
+    if output not in ("reference", "embedding"):
+        raise ValueError("output %r: 'reference' or 'embedding'" % (output,))
+    eng = model.engine
+    n = 0
+    with open(path, "w", encoding="utf-8") as w:
+        for bi, pair in enumerate(batches):
+            e1, e2, _, _ = model.predict(**_pair_args(pair, eng.use_image), noise=noise[bi] if noise is not None else None,
+                                         seed=int(seed) + bi, embeddings=output == "embedding")
+            e1, e2 = e1.detach().cpu().numpy(), e2.detach().cpu().numpy()
+            for i1, i2, a, b in zip(pair["item_ids_1"], pair["item_ids_2"], e1, e2):
+                w.write(json.dumps({"src_item_id": i1, "src_item_emb": _emb_field(a), "tgt_item_id": i2,
+                                    "tgt_item_emb": _emb_field(b), "threshold": threshold}) + "\n")
+                n += 1
+    return n

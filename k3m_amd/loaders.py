@@ -250,3 +250,74 @@ class ConceptCapLoaderVal_struc(_LoaderBase):
             v_feature_size, v_target_size, v_loc_size, visual_target, batch_size, objective, visualization,
             shuffle=False, seed=seed, device=device, local_rank=local_rank, records=records,
             synthetic_regions=synthetic_regions)
+
+
+# ---------------------------------------------------------------- item-alignment pairs (fine-tuning)
+def write_pair_records(path, pairs, max_boxes=36, v_feature_size=2048, v_target_size=1601):
+    """Store labelled pairs ``(label, item-1 record, item-2 record)`` (10-field records as in write_records) as two
+    write_records directories ``item_1/`` and ``item_2/`` plus ``label.npy``."""
+    pairs = list(pairs)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "label.npy"), np.array([float(p[0]) for p in pairs], np.float32))
+    for k in (1, 2):
+        write_records(os.path.join(path, "item_%d" % k), [p[k] for p in pairs], max_boxes, v_feature_size,
+                      v_target_size)
+
+
+class PairRecordDir(object):
+    """Random access to a write_pair_records directory: the 21-field rows K3MPreprocessBatch takes."""
+
+    def __init__(self, path):
+        self.label = np.load(os.path.join(path, "label.npy"), allow_pickle=False)
+        self.items = (RecordDir(os.path.join(path, "item_1")), RecordDir(os.path.join(path, "item_2")))
+        if not len(self.label) == len(self.items[0]) == len(self.items[1]):
+            raise ValueError("%s: label.npy, item_1 and item_2 differ in length" % path)
+
+    def __len__(self):
+        return len(self.label)
+
+    def __getitem__(self, i):
+        return (float(self.label[i]),) + self.items[0][i] + self.items[1][i]
+
+
+class K3MDataLoader(object):
+    """Drop-in for the reference's fine-tuning loader (concept_cap_dataset_struc.py:201-217 constructor): iterates
+    device pair dicts with K3MForItemAlignment.forward's argument names (plus image_target_1/2) and the two item-id
+    lists as "item_ids_1" / "item_ids_2".  Built on K3MPreprocessBatch.prepare + PairCollator (collation on the
+    GPU).  Records: a write_pair_records directory at os.path.join(corpus_path, file_name), or ``records=`` (any
+    sequence of 21-field rows).  ``serializer`` / ``num_workers`` are accepted and unused (the LMDB container is not
+    read); ``shuffle`` as LMDBSerializer.load(shuffle=True) by default, seeded by ``seed``."""
+
+    def __init__(self, corpus_path, file_name, tokenizer, max_seq_len=32, max_seq_len_pv=32, max_num_pv=20,
+                 max_region_len=36, v_feature_size=2048, v_target_size=1601, v_loc_size=5, batch_size=512,
+                 num_workers=25, serializer=None, visual_target=0, device=None, records=None, shuffle=True, seed=None):
+        from .data import K3MPreprocessBatch, PairCollator
+        if records is None:
+            path = os.path.join(corpus_path, file_name) if corpus_path else file_name
+            if not os.path.exists(os.path.join(path, "label.npy")):
+                raise NotImplementedError(
+                    "%s: not a pair record directory (k3m_amd.loaders.write_pair_records); the tensorpack LMDB "
+                    "container is not read by this build" % path)
+            records = PairRecordDir(path)
+        self.records = records
+        self.num_dataset = len(records)
+        self.batch_size, self.num_workers, self.shuffle = int(batch_size), num_workers, shuffle
+        self._order_rng = random.Random(seed)
+        self.pre = K3MPreprocessBatch(tokenizer, max_seq_len=max_seq_len, max_seq_len_pv=max_seq_len_pv,
+                                      max_num_pv=max_num_pv, max_region_len=max_region_len,
+                                      v_feature_size=v_feature_size, v_target_size=v_target_size,
+                                      v_loc_size=v_loc_size, visual_target=visual_target)
+        self.collate = PairCollator(_device_of(device, -1), max_region_len, v_feature_size, v_target_size,
+                                    visual_target)
+
+    def __len__(self):
+        return (self.num_dataset + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        order = list(range(self.num_dataset))
+        if self.shuffle:
+            self._order_rng.shuffle(order)
+        for s in range(0, len(order), self.batch_size):
+            pair, ids1, ids2 = self.collate([self.pre.prepare(self.records[i]) for i in order[s:s + self.batch_size]])
+            pair["item_ids_1"], pair["item_ids_2"] = ids1, ids2
+            yield pair

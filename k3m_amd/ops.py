@@ -503,11 +503,20 @@ def ln_bwd(dy, xhat, rstd, gamma, dres, dx, dgamma, dbeta, p_in=0.0, p_out=0.0, 
 
 
 def embed_fwd(ids, tt, word, pos, typ, gamma, beta, y0, y1, y2, xhat, rstd, p_out, seed, off, eps=1e-12):
+    """xhat = rstd = None: the forward-only kernel form.  y1 / y2 may then be bf16 beside an fp32 y0 (the encoder
+    copies written in the encoder dtype: the bits of convert() of the fp32 row)."""
     nseq, ln = ids.shape
     if _debug.ON:
         _debug.check_range(ids, 0, word.shape[0], "embedding ids")
         _debug.check_range(tt, 0, typ.shape[0], "token type ids")
         _debug.check_len(ln, pos.shape[0], "sequence length")
+    y1t = next((t for t in (y1, y2) if t is not None), y0)
+    assert y1 is None or y2 is None or y1.dtype == y2.dtype
+    if y1t.dtype != y0.dtype:
+        call("k3m_embed_fwd_ex", ptr(ids), ptr(tt), ptr(word), ptr(pos), ptr(typ), ptr(gamma), ptr(beta), ptr(y0),
+             ptr(y1), ptr(y2), ptr(xhat), ptr(rstd), nseq, ln, word.shape[1], eps, p_out, seed, off, dt(y0), dt(y1t),
+             stream())
+        return
     call("k3m_embed_fwd", ptr(ids), ptr(tt), ptr(word), ptr(pos), ptr(typ), ptr(gamma), ptr(beta), ptr(y0), ptr(y1),
          ptr(y2), ptr(xhat), ptr(rstd), nseq, ln, word.shape[1], eps, p_out, seed, off, dt(y0), stream())
 
