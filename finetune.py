@@ -22,7 +22,12 @@ Differences, each stated:
   ``--k3m_synthetic_regions SEED`` (accepted for symmetry with train.py; pair records carry their regions),
   ``--k3m_max_steps N``, ``--k3m_pred_output {reference,embedding}`` (``embedding``: c_final of both items for every
   loss type) and the parity harness ``--k3m_parity_case NPZ``: a ``golden_ft_*`` fixture's pair, weights and gumbel
-  noise are fed in place of the loaders (tests/test_gpu_finetune_driver.py).
+  noise are fed in place of the loaders (tests/test_gpu_finetune_driver.py);
+* ``--do_retrieve`` (the reference has no retrieval step): both items of every ``valid`` pair are embedded,
+  the item-2 side is indexed and searched with the item-1 side (``k3m_amd.retrieve``, cosine), one JSON line per pair
+  ``{"src_item_id", "tgt_item_ids", "scores"}`` with ``--k3m_topk`` (default 10) ids goes to
+  ``--k3m_retrieve_output`` (default ``retrieval_top<k>.jsonl`` beside the predictions) and Rank@1/5/10 over the
+  pairs with label 1 is logged.
 """
 import argparse
 import logging
@@ -94,6 +99,24 @@ def build_parser():
     return p
 
 
+def build_retrieve_parser():
+    """The retrieval step's options.  A parser of their own: build_parser() stays the reference's
+    surface plus the build-side options, which tests/test_finetune_cli.py pins option by option."""
+    p = argparse.ArgumentParser(add_help=False)
+    p.add_argument("--do_retrieve", action="store_true")
+    p.add_argument("--k3m_topk", default=10, type=int)
+    p.add_argument("--k3m_retrieve_output", default="", type=str)
+    return p
+
+
+def parse_args(argv=None):
+    """The driver's whole command line -> (args of build_parser(), the retrieval options): the retrieval options
+    are taken out first, build_parser() reads the rest (and rejects what neither knows).  Two namespaces, so that
+    what the driver records of ``args`` (hyperparamter.txt) is what it was."""
+    rargs, rest = build_retrieve_parser().parse_known_args(argv)
+    return build_parser().parse_args(rest), rargs
+
+
 def _parity_inputs(path, dev):
     """(pair dict with item ids, noise pair, fixture) of a golden_ft_* case (tests/golden/make_finetune_golden.py)."""
     d = np.load(path, allow_pickle=False)
@@ -127,7 +150,7 @@ def _parity_inputs(path, dev):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args, rargs = parse_args(argv)
     from k3m_amd import checkpoint as C
     from k3m_amd.config import finetune_config
     from k3m_amd.finetune import ItemAlignmentTrainer, evaluate, save_model, write_predictions
@@ -178,7 +201,7 @@ def main(argv=None):
         if args.do_train:
             train_loader = K3MDataLoader(args.data_dir, args.file_name.format("train"), tokenizer,
                                          batch_size=args.train_batch_size, **lkw)
-        if args.do_eval or args.do_pred:
+        if args.do_eval or args.do_pred or rargs.do_retrieve:
             valid_loader = K3MDataLoader(args.data_dir, args.file_name.format("valid"), tokenizer,
                                          batch_size=args.eval_batch_size, shuffle=False, **lkw)
 
@@ -243,6 +266,16 @@ def main(argv=None):
         n = write_predictions(model, valid_batches(), path, args.threshold, output=args.k3m_pred_output,
                               noise=[parity[1]] if parity is not None else None, seed=args.seed)
         logger.info(f"[Prediction] Finished prediction: {n} pairs -> {path}")
+
+    if rargs.do_retrieve:
+        from k3m_amd.retrieve import retrieve_pairs
+        path = rargs.k3m_retrieve_output or os.path.join(output_model_path, f"retrieval_top{rargs.k3m_topk}.jsonl")
+        n, ranks = retrieve_pairs(model, valid_batches(), path, k=rargs.k3m_topk,
+                                  noise=[parity[1]] if parity is not None else None, seed=args.seed)
+        logger.info(f"[Retrieval] {n} queries -> {path}")
+        line = ", ".join(f"Rank@{k.split('@')[1]}={v:.4f}" for k, v in ranks.items())
+        logger.info(f"[Retrieval] {line}")
+        print(f"[Retrieval] {line}", flush=True)
     return 0
 
 

@@ -464,6 +464,23 @@ int k3m_align_ce_fwd(const float* u, const float* W, const float* bias, const fl
 int k3m_align_cosine_fwd(const float* e, const float* labels, int B, int H, float margin, float* loss, float* probs,
                          float* loss_rows, hipStream_t stream);
 
+/* ---- Top-k item retrieval over item embeddings ---------------------------------
+ * For every row of Q [nq][h] the k best rows of the catalogue C [nc][h] (both fp32 row-major, 16-B aligned,
+ * h % 4 == 0, 4 <= h <= 4096, 1 <= k <= 64) by inner product or cosine (norms clamped at 1e-8: a zero vector
+ * scores 0), fused: the similarity tiles come out of exact-f32 MFMA accumulators and go straight into a running
+ * top-k, the [nq][nc] score matrix is never stored.  scores [nq][k] fp32 / idx [nq][k] int64: every row sorted
+ * by descending score, equal scores by ascending index; reported index = c_base + catalogue row; slots past the
+ * number of eligible rows hold (-inf, -1).  q_ids (int64 [nq], or NULL): query i skips the row whose reported
+ * index equals q_ids[i] (-1: none).  accumulate != 0: the incoming scores / idx are an earlier result (of other
+ * catalogue blocks) and are merged with this block's candidates.  chunks: into how many pieces the catalogue is
+ * split across workgroups (0 = choose); the result is bit-identical for every value, and for every split of a
+ * catalogue into accumulate blocks.  ws: k3m_topk_sim_ws_bytes(...) bytes, 16-B aligned. */
+enum K3mTopkMetric { K3M_TOPK_INNER = 0, K3M_TOPK_COSINE = 1 };
+int k3m_topk_sim_ws_bytes(int nq, int nc, int h, int k, int chunks, long long* bytes);
+int k3m_topk_sim(const float* q, const float* c, int nq, int nc, int h, int k, int metric, long long c_base,
+                 const long long* q_ids, int accumulate, int chunks, float* scores, long long* idx, void* ws,
+                 long long ws_bytes, hipStream_t stream);
+
 /* ---- Data path ------------------------------------------------------
  * Global-region collation of a batch of region features, fused with mask_region's feature
  * zeroing: replaces the numpy block of ConceptCapLoaderTrain_struc.__iter__

@@ -124,6 +124,8 @@ SIGNATURES = {
     "k3m_align_cosine_fwd_bwd": [vp, vp, i32, i32, f32, vp, vp, vp, vp, vp],
     "k3m_align_ce_fwd": [vp, vp, vp, vp, i32, i32, f32, u64, u64, vp, vp, vp, vp, vp],
     "k3m_align_cosine_fwd": [vp, vp, i32, i32, f32, vp, vp, vp, vp],
+    "k3m_topk_sim_ws_bytes": [i32, i32, i32, i32, i32, vp],
+    "k3m_topk_sim": [vp, vp, i32, i32, i32, i32, i32, i64, vp, i32, i32, vp, vp, vp, i64, vp],
 }
 
 _lib = None

@@ -718,3 +718,61 @@ def dyn_scale_bwd(dqkv, qkv, z, dz, rows):
     call("k3m_dyn_scale_bwd", ptr(dqkv), _ld(dqkv), ptr(qkv), _ld(qkv), ptr(z), ptr(dz), nseq, rows, hv2 // 2, dt(qkv),
          stream())
     return dz
+
+
+# ------------------------------------------------------------------ top-k item retrieval (topk.hip)
+TOPK_METRICS = {"inner": 0, "cosine": 1}   # K3mTopkMetric
+TOPK_MAX_K = 64
+
+
+def topk_sim(q, c, k, metric="cosine", c_base=0, q_ids=None, out=None, accumulate=False, chunks=0):
+    """(scores [Nq, k] fp32, idx [Nq, k] int64): for every row of q [Nq, H] the k most similar rows of the catalogue
+    c [Nc, H] (fp32, contiguous) by inner product or cosine, fused (no [Nq, Nc] score matrix).  Rows are sorted by
+    descending score, equal scores by ascending index; idx = c_base + catalogue row; slots past the number of
+    eligible rows hold (-inf, -1).  q_ids (int64 [Nq]): query i never retrieves the row whose idx equals q_ids[i]
+    (-1: excludes nothing).  out: the (scores, idx) pair to write; accumulate=True: out holds an earlier result,
+    which is merged with this catalogue block's candidates (block-by-block search with c_base advancing).  chunks:
+    the number of catalogue pieces dealt to workgroups (0: chosen from the shapes); every value gives the same bits.
+    Every argument is checked here, before any library call (ValueError)."""
+    if metric not in TOPK_METRICS:
+        raise ValueError("metric %r: 'inner' or 'cosine'" % (metric,))
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= TOPK_MAX_K:
+        raise ValueError("k = %r: an int in [1, %d]" % (k, TOPK_MAX_K))
+    for name, t in (("q", q), ("c", c)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError("%s: a 2-D tensor [rows, H] expected" % name)
+        if t.dtype != torch.float32:
+            raise ValueError("%s: dtype %s, float32 expected" % (name, t.dtype))
+        if not t.is_contiguous():
+            raise ValueError("%s: contiguous rows expected" % name)
+    if q.shape[1] != c.shape[1]:
+        raise ValueError("H differs: q has %d columns, c has %d" % (q.shape[1], c.shape[1]))
+    H = q.shape[1]
+    if H % 4 != 0 or not 4 <= H <= 4096:
+        raise ValueError("H = %d: a multiple of 4 in [4, 4096]" % H)
+    if q.device != c.device:
+        raise ValueError("q and c are on different devices")
+    if not isinstance(chunks, int) or chunks < 0:
+        raise ValueError("chunks = %r: an int >= 0" % (chunks,))
+    nq, nc = q.shape[0], c.shape[0]
+    if nq >= 2 ** 31 or nc >= 2 ** 31:
+        raise ValueError("at most 2^31 - 1 rows per call (search a larger catalogue block by block)")
+    if q_ids is not None and (not isinstance(q_ids, torch.Tensor) or q_ids.dtype != torch.int64
+                              or q_ids.shape != (nq,) or not q_ids.is_contiguous() or q_ids.device != q.device):
+        raise ValueError("q_ids: a contiguous int64 [Nq] tensor on q's device expected")
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs the earlier result in out=(scores, idx)")
+    else:
+        s, i = out
+        if (s.dtype != torch.float32 or i.dtype != torch.int64 or s.shape != (nq, k) or i.shape != (nq, k)
+                or not s.is_contiguous() or not i.is_contiguous() or s.device != q.device or i.device != q.device):
+            raise ValueError("out: contiguous (float32 [Nq, k], int64 [Nq, k]) on q's device expected")
+    if out is None:
+        out = (empty((nq, k), q), empty((nq, k), q, dtype=torch.int64))
+    nb = C.c_longlong(0)
+    call("k3m_topk_sim_ws_bytes", nq, nc, H, k, chunks, C.addressof(nb))
+    ws = torch.empty((max(int(nb.value), 16),), dtype=torch.uint8, device=q.device)
+    call("k3m_topk_sim", ptr(q), ptr(c), nq, nc, H, k, TOPK_METRICS[metric], int(c_base), ptr(q_ids), int(accumulate),
+         chunks, ptr(out[0]), ptr(out[1]), ptr(ws), int(nb.value), stream())
+    return out
