@@ -481,6 +481,22 @@ int k3m_topk_sim(const float* q, const float* c, int nq, int nc, int h, int k, i
                  const long long* q_ids, int accumulate, int chunks, float* scores, long long* idx, void* ws,
                  long long ws_bytes, hipStream_t stream);
 
+/* ---- Masked-position prediction: fused vocabulary top-k --------------------------
+ * For every row of x [n][h] and the decoder w [v][h] (both fp32 row-major, 16-B aligned, h % 4 == 0,
+ * 4 <= h <= 4096, v >= 1), with bias [v] or NULL, the k largest logits x . w[j] + bias[j] (1 <= k <= 32: the
+ * per-lane list of a wider k is not built, see §22.2), fused: the logit tiles come out of exact-f32 MFMA
+ * accumulators and go straight into a running top-k and an online log-sum-exp, the [n][v] logits are never stored.
+ * scores [n][k] fp32 / idx [n][k] int64: every row sorted by descending logit, equal logits by ascending j; slots
+ * past v hold (-inf, -1).  lse [n]: log sum_j exp(logit_j) over all v.  gold (int64 [n]) and gold_score [n], both
+ * or neither: gold_score[i] = the logit of row gold[i], -inf where gold[i] is -1 (or outside [0, v)).  chunks: into
+ * how many pieces the vocabulary is split across workgroups (0 = choose); scores, idx and gold_score are
+ * bit-identical for every value, lse is deterministic for a given value (summation rounding apart across values).
+ * ws: k3m_topk_logits_ws_bytes(...) bytes, 16-B aligned.  n == 0 is a no-op.  No atomics. */
+int k3m_topk_logits_ws_bytes(int n, int v, int h, int k, int chunks, long long* bytes);
+int k3m_topk_logits(const float* x, const float* w, const float* bias, int n, int v, int h, int k,
+                    const long long* gold, int chunks, float* scores, long long* idx, float* lse, float* gold_score,
+                    void* ws, long long ws_bytes, hipStream_t stream);
+
 /* ---- Data path ------------------------------------------------------
  * Global-region collation of a batch of region features, fused with mask_region's feature
  * zeroing: replaces the numpy block of ConceptCapLoaderTrain_struc.__iter__

@@ -1180,6 +1180,24 @@ class K3MEngine(object):
         from . import infer
         return infer.embed(self, batch, noise=noise, seed=seed, groups=groups)
 
+    def predict_masked(self, batch, k=10, rows="labels", noise=None, seed=None, mask_id=103):
+        """What the model predicts at masked positions: the eval-mode, forward-only encoder and fusion
+        of embed(), then the MLM head (BertLMPredictionHead, vilbert_k3m.py:1821-1839) and the region head
+        (:1912-1924) on the selected rows alone, their decoders fused with a top-k, the log-sum-exp and the gold
+        logit (ops.topk_logits: no [rows, vocabulary] logits are stored).
+
+        rows: "labels" (lm_label_ids* != -1, image_label == 1), "mask" (token id == mask_id in title and PV; no
+        label field is read, regions only if image_label is present) or a dict {"t" / "pv" / "v": int64 [n, 2] of
+        (item, position)}; rows come in compaction order (title rows, then PV rows, row-major).
+        Returns {"t", "pv", "v"}, each {pos [n, 2], idx [n, k], logprob [n, k] (logit - lse), lse [n]} and, where
+        a gold is known (the label id; the argmax class of image_target), gold [n] and gold_logprob [n].  "v" is
+        absent without the image modality and with visual_target=1 (a regression has no classes).
+        The decoders run exact-f32 on the fp32 master weights in a bf16 engine too: those logits are not the bf16
+        training logits bit for bit.  Nothing is kept for a backward, fp.grad is untouched and a pending forward's
+        ctx is left alone; an item-alignment engine raises ValueError (no heads).  k3m_amd/predict.py."""
+        from . import predict
+        return predict.predict_masked(self, batch, k=k, rows=rows, noise=noise, seed=seed, mask_id=mask_id)
+
     # ------------------------------------------------------------ backward
     def backward(self, ctx, w_mlm=1.0, w_img=1.0, w_lpm=1.0, grad_ready=None, w_mlm_pv=None):
         """Backward of  w_mlm*(mlm_t + mlm_pv) + w_img*img + w_lpm*lpm  (train_concap_struc.py:533); with

@@ -48,10 +48,12 @@ def infer_plan(cfg, dedup=True):
     return plan
 
 
-def embed(eng, batch, noise=None, seed=None, groups=1):
-    """K3MEngine.embed; see there."""
+def sequences(eng, batch, noise=None, seed=None):
+    """The eval-mode, forward-only encoder and fusion up to the fused sequences: (seq_tp [B T + B P, H] fp32, the
+    title rows then the PV rows; seq_v [B R, Hv] fp32, None without the image modality; rng, the call's draw
+    state).  The part embed() and predict_masked() (k3m_amd/predict.py) share."""
     if not eng.use_image:
-        return _embed_text(eng, batch, noise, seed, groups)
+        return _sequences_text(eng, batch, noise, seed)
     c, fp, dev = eng.cfg, eng.fp, eng.device
     if debug.ON:
         debug.check_batch(batch, c)
@@ -161,7 +163,19 @@ def embed(eng, batch, noise=None, seed=None, groups=1):
     streams = {"v": (ind_v, v1, v2, seq_v, Hv), "t": (ind_t, t1, t3, seq_tp[0:BT], H),
                "pv": (ind_pv, p2, p3, seq_tp[BT:], H)}
     eng._fusion_fwd(streams, noise, rng, save=False)
-    del streams, XT, XV, t1, t3, p2, p3, v1, v2
+    return seq_tp, seq_v, rng
+
+
+def embed(eng, batch, noise=None, seed=None, groups=1):
+    """K3MEngine.embed; see there."""
+    if not eng.use_image:
+        return _embed_text(eng, batch, noise, seed, groups)
+    dev, H, Hv = eng.device, eng.H, eng.Hv
+    seq_tp, seq_v, rng = sequences(eng, batch, noise, seed)
+    B, T = batch["input_ids"].shape
+    P, R = batch["input_ids_pv"].shape[1], batch["image_feat"].shape[1]
+    BT = B * T
+    f32 = dict(dtype=torch.float32, device=dev)
     mean_v = torch.empty((B, Hv), **f32)
     pooled_t = torch.empty((B, H), **f32)
     pooled_pv = torch.empty((B, H), **f32)
@@ -177,9 +191,9 @@ def embed(eng, batch, noise=None, seed=None, groups=1):
             "pooled_v": pooled_v}
 
 
-def _embed_text(eng, batch, noise, seed, groups):
-    """embed() of the model without the image modality (k3m_amd/engine_text.py's layout: one [title | PV] buffer, no
-    duplicated stream, so nothing merges)."""
+def _sequences_text(eng, batch, noise, seed):
+    """sequences() of the model without the image modality (k3m_amd/engine_text.py's layout: one [title | PV] buffer,
+    no duplicated stream, so nothing merges)."""
     from . import engine_text
     c, fp, dev = eng.cfg, eng.fp, eng.device
     if debug.ON:
@@ -219,7 +233,17 @@ def _embed_text(eng, batch, noise, seed, groups):
         XT = ops.convert(XT, torch.empty((Nt, H), **f32))
     seq_tp = torch.empty((Nt, H), **f32)
     engine_text.gate_fwd(eng, ind, XT, seq_tp, noise, rng, BT, BP, save=False)
-    del XT, ind
+    return seq_tp, None, rng
+
+
+def _embed_text(eng, batch, noise, seed, groups):
+    """embed() of the model without the image modality."""
+    dev, H = eng.device, eng.H
+    seq_tp, _, rng = _sequences_text(eng, batch, noise, seed)
+    B, T = batch["input_ids"].shape
+    P = batch["input_ids_pv"].shape[1]
+    BT = B * T
+    f32 = dict(dtype=torch.float32, device=dev)
     pooled_t = torch.empty((B, H), **f32)
     pooled_pv = torch.empty((B, H), **f32)
     L.call("k3m_seq_mean", seq_tp.data_ptr(), B, T, 1, H, 1.0, pooled_t.data_ptr(), 0, L.F32, L.stream())

@@ -776,3 +776,54 @@ def topk_sim(q, c, k, metric="cosine", c_base=0, q_ids=None, out=None, accumulat
     call("k3m_topk_sim", ptr(q), ptr(c), nq, nc, H, k, TOPK_METRICS[metric], int(c_base), ptr(q_ids), int(accumulate),
          chunks, ptr(out[0]), ptr(out[1]), ptr(ws), int(nb.value), stream())
     return out
+
+
+# ------------------------------------------------------------------ masked-position prediction (topk_logits.hip)
+TOPK_LOGITS_MAX_K = 32
+
+
+def topk_logits(x, W, bias=None, k=10, gold=None, chunks=0):
+    """(scores [n, k] fp32, idx [n, k] int64, lse [n] fp32, gold_score [n] fp32 | None): for every row of x [n, H]
+    the k largest logits x . W[j] + bias[j] over the decoder W [v, H] (fp32, contiguous; bias [v] or None), the
+    log-sum-exp over all v logits and, with gold (int64 [n]), the logit of row gold[i] (-inf where gold[i] == -1),
+    fused: the [n, v] logits are never stored.  Rows are sorted by descending logit, equal logits by
+    ascending index; slots past v hold (-inf, -1).  chunks: the number of vocabulary pieces dealt to workgroups
+    (0: chosen from the shapes); scores, idx and gold_score have the same bits for every value.  Every argument is
+    checked here, before any library call (ValueError)."""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= TOPK_LOGITS_MAX_K:
+        raise ValueError("k = %r: an int in [1, %d]" % (k, TOPK_LOGITS_MAX_K))
+    for name, t in (("x", x), ("W", W)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError("%s: a 2-D tensor [rows, H] expected" % name)
+        if t.dtype != torch.float32:
+            raise ValueError("%s: dtype %s, float32 expected" % (name, t.dtype))
+        if not t.is_contiguous():
+            raise ValueError("%s: contiguous rows expected" % name)
+    if x.shape[1] != W.shape[1]:
+        raise ValueError("H differs: x has %d columns, W has %d" % (x.shape[1], W.shape[1]))
+    H = x.shape[1]
+    if H % 4 != 0 or not 4 <= H <= 4096:
+        raise ValueError("H = %d: a multiple of 4 in [4, 4096]" % H)
+    if x.device != W.device:
+        raise ValueError("x and W are on different devices")
+    if isinstance(chunks, bool) or not isinstance(chunks, int) or chunks < 0:
+        raise ValueError("chunks = %r: an int >= 0" % (chunks,))
+    n, v = x.shape[0], W.shape[0]
+    if v < 1 or n >= 2 ** 31 or v >= 2 ** 31:
+        raise ValueError("1 <= v and at most 2^31 - 1 rows per call")
+    if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or bias.shape != (v,)
+                             or not bias.is_contiguous() or bias.device != x.device):
+        raise ValueError("bias: a contiguous float32 [v] tensor on x's device expected")
+    if gold is not None and (not isinstance(gold, torch.Tensor) or gold.dtype != torch.int64 or gold.shape != (n,)
+                             or not gold.is_contiguous() or gold.device != x.device):
+        raise ValueError("gold: a contiguous int64 [n] tensor on x's device expected")
+    scores = empty((n, k), x)
+    idx = empty((n, k), x, dtype=torch.int64)
+    lse = empty((n,), x)
+    gs = empty((n,), x) if gold is not None else None
+    nb = C.c_longlong(0)
+    call("k3m_topk_logits_ws_bytes", n, v, H, k, chunks, C.addressof(nb))
+    ws = torch.empty((max(int(nb.value), 16),), dtype=torch.uint8, device=x.device)
+    call("k3m_topk_logits", ptr(x), ptr(W), ptr(bias), n, v, H, k, ptr(gold), chunks, ptr(scores), ptr(idx), ptr(lse),
+         ptr(gs), ptr(ws), int(nb.value), stream())
+    return scores, idx, lse, gs

@@ -250,6 +250,10 @@ class Trainer(object):
             out["masked_img_loss"] * self.loss_img_weight
         return out
 
+    def predict_masked(self, batch, **kw):
+        """K3MEngine.predict_masked on a validation batch (k, rows, noise, seed, mask_id pass through)."""
+        return self.engine.predict_masked(batch, **kw)
+
     # ---------------------------------------------------------------- schedule
     def current_lr(self):
         """lr of the next optimizer step for a multiplier-1 tensor of the first group."""

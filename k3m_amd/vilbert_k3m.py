@@ -196,3 +196,36 @@ class BertForMultiModalPreTraining_tri_stru(nn.Module):
         kw = {"noise": gumbel_noise, "ent_neg": ent_neg, "val_neg": val_neg}
         mlm_t, img, mlm_pv, nsp, c_init, c_final, lpm = _Step.apply(self._anchor, self, batch, kw)
         return (mlm_t, img, 0, mlm_pv, 0, 0, nsp, c_init, c_final, lpm)
+
+    def predict_masked(self, input_ids, image_feat=None, image_loc=None, token_type_ids=None, attention_mask=None,
+                       image_attention_mask=None, masked_lm_labels=None, image_label=None, image_target=None,
+                       input_ids_pv=None, token_type_ids_pv=None, attention_mask_pv=None, masked_lm_labels_pv=None,
+                       index_p=None, index_v=None, gumbel_noise=None, k=10, rows="labels", noise=None, seed=None,
+                       mask_id=103):
+        """What the model predicts at masked positions (K3MEngine.predict_masked): forward()'s argument names, the
+        label arguments optional (rows="labels" needs them; rows="mask" and explicit positions do not).  noise is
+        gumbel_noise under the engine's name; either may be given."""
+        dev = self.engine.device
+
+        def d(t, like=None):
+            if t is None:
+                return torch.ones_like(like) if like is not None else None
+            return torch.as_tensor(t).to(dev)
+        ids, pids = d(input_ids), d(input_ids_pv)
+        batch = dict(input_ids=ids, input_mask=d(attention_mask, ids), input_ids_pv=pids,
+                     input_mask_pv=d(attention_mask_pv, pids),
+                     segment_ids=d(token_type_ids) if token_type_ids is not None else torch.zeros_like(ids),
+                     segment_ids_pv=d(token_type_ids_pv) if token_type_ids_pv is not None else torch.zeros_like(pids),
+                     index_p=d(index_p), index_v=d(index_v))
+        if self.engine.use_image:
+            batch.update(image_feat=d(image_feat).float(), image_loc=d(image_loc).float())
+            B, R = batch["image_feat"].shape[:2]
+            batch["image_mask"] = (d(image_attention_mask) if image_attention_mask is not None
+                                   else torch.ones((B, R), dtype=torch.int64, device=dev))
+        optional = dict(lm_label_ids=masked_lm_labels, lm_label_ids_pv=masked_lm_labels_pv, image_label=image_label,
+                        image_target=image_target)
+        for name, t in optional.items():
+            if t is not None:
+                batch[name] = d(t).float() if name == "image_target" else d(t)
+        return self.engine.predict_masked(batch, k=k, rows=rows, noise=noise if noise is not None else gumbel_noise,
+                                          seed=seed, mask_id=mask_id)

@@ -19,7 +19,10 @@ Differences, each stated:
   LMDB container is not read);
 * build-side options, all prefixed ``--k3m_``: ``--k3m_char_tokenizer`` (no vocab.txt offline),
   ``--k3m_synthetic_regions SEED`` (region features for TSV rows), ``--k3m_no_shuffle``,
-  ``--k3m_max_steps N``, ``--k3m_loss_log PATH`` (one JSON line per step), and the parity harness
+  ``--k3m_max_steps N``, ``--k3m_loss_log PATH`` (one JSON line per step), ``--k3m_eval_topk K`` with
+  ``--do_eval`` (after the validation losses: what the model predicts at the masked positions of the validation
+  set, logged as title / PV / region accuracy@1/5/K and gold NLL; ``--k3m_pred_output PATH`` also writes one JSON
+  line per predicted position), and the parity harness
   ``--k3m_parity_case NPZ``: every step feeds the fixture's recorded batch with its gumbel noise and LPM
   negatives, dropout off (the golden vectors were recorded with model.eval(); tests/test_gpu_train_driver.py);
 * ``--text_only``: the model without the image modality (``config.use_image = False``, the reference's
@@ -98,6 +101,11 @@ def get_parser(argv=None):
     p.add_argument("--k3m_max_steps", default=0, type=int)
     p.add_argument("--k3m_loss_log", default="", type=str)
     p.add_argument("--k3m_parity_case", default="", type=str)
+    p.add_argument("--k3m_eval_topk", default=0, type=int,
+                   help="with --do_eval: also predict the masked positions of the validation set and log title / PV / "
+                        "region accuracy@1/5/K and the gold NLL (0: off)")
+    p.add_argument("--k3m_pred_output", default="", type=str,
+                   help="with --k3m_eval_topk: write one JSON line per predicted position to this file")
     p.add_argument("--text_only", action="store_true",
                    help="train the model without the image modality (config.use_image = False): title + "
                         "property-value knowledge only; the loaders' image fields are ignored")
@@ -300,12 +308,24 @@ def main(argv=None):
         trainer.finish()   # the epoch's outstanding label-count / loss checks (synchronising)
         if args.do_eval and valid_loader is not None:
             logger.info(f"[Epoch-{epoch}] Starting evaluation ...")
+            pred = None
+            if args.k3m_eval_topk:
+                from k3m_amd.predict import MaskedEval, STREAM_NAMES
+                pred = MaskedEval(args.k3m_eval_topk, args.k3m_pred_output if default_gpu else "")
             for step, (batch, _ids) in enumerate(valid_loader.batches()):
                 out = trainer.evaluate(batch)
                 logger.info(f"[Eval] [Epoch-{epoch}] loss: {_trunc(out['loss'])} "
                             f"loss_t: {_trunc(out['masked_lm_loss'])}, "
                             f"loss_v: {_trunc(float(out['masked_img_loss']) * args.loss_img_weight)}, "
                             f"loss_pv: {_trunc(out['masked_lm_loss_pv'])}, loss_tri: {_trunc(out['loss_lpm'])}")
+                if pred is not None:
+                    pred.add(trainer.predict_masked(batch, k=args.k3m_eval_topk), _ids)
+            if pred is not None:
+                pred.close()
+                for name, m in pred.summary().items():
+                    accs = " ".join(f"acc@{kk}: {_trunc(m['acc@%d' % kk])}" for kk in pred.ks)
+                    logger.info(f"[Eval] [Epoch-{epoch}] {STREAM_NAMES[name]} {accs} nll: {_trunc(m['nll'])} "
+                                f"rows: {m['n']}")
         if default_gpu:
             logger.info(f"[Epoch-{epoch}] saving model")
             base = os.path.join(output_model_path, f"K3M_struc_presample-{args.if_pre_sampling}_epoch-{epoch}")
