@@ -464,6 +464,33 @@ int k3m_align_ce_fwd(const float* u, const float* W, const float* bias, const fl
 int k3m_align_cosine_fwd(const float* e, const float* labels, int B, int H, float margin, float* loss, float* probs,
                          float* loss_rows, hipStream_t stream);
 
+/* ---- Item classification fine-tuning --------------------------------------------
+ * ClassificationHead (vilbert_k3m.py:2164-2183) over one item's e = c_final [B][H] and a C-way cross entropy.
+ * Element-wise, fp32, the dropout factor of element (b, c) drawn at counter off + b * H + c (p == 0: all ones):
+ *   drop_fwd       x  = e * keep                       drop_bwd       de = dx * keep
+ *   tanh_drop_fwd  h  = tanh(u) * keep                 tanh_drop_bwd  du = dh * keep * (1 - tanh(u)^2)
+ * (tanh is recomputed from u; no mask and no tanh(u) is stored).  16-byte accesses when H % 4 == 0 and the
+ * pointers are 16-B aligned, one element per thread otherwise.  The output may alias an input.  B == 0 is a no-op. */
+int k3m_cls_drop_fwd(const float* e, int B, int H, float p, uint64_t seed, uint64_t off, float* x,
+                     hipStream_t stream);
+int k3m_cls_drop_bwd(const float* dx, int B, int H, float p, uint64_t seed, uint64_t off, float* de,
+                     hipStream_t stream);
+int k3m_cls_tanh_drop_fwd(const float* u, int B, int H, float p, uint64_t seed, uint64_t off, float* h,
+                          hipStream_t stream);
+int k3m_cls_tanh_drop_bwd(const float* dh, const float* u, int B, int H, float p, uint64_t seed, uint64_t off,
+                          float* du, hipStream_t stream);
+/* loss = F.cross_entropy(z, labels, weight, ignore_index = -1, label_smoothing = eps), mean reduction, over the
+ * logits z [rows][C] (row stride ld >= C floats), labels int64 [rows] (-1: unlabelled), weight [C] or NULL (ones),
+ * 0 <= eps < 1.  Writes loss_rows [rows] (the undivided row terms), lse [rows], loss [1], pred [rows] (int32 argmax,
+ * the lowest index among equal logits) and denom [2] = (S = sum of w[label] over the labelled rows, sum_c w_c).
+ * fwd_bwd overwrites z with dz = d loss / d z (zero rows for unlabelled items); fwd leaves z as it is and gives the
+ * same loss, lse and pred bits.  S == 0: loss 0 and dz 0 (torch: NaN).  A label outside {-1, 0 .. C-1}: a NaN
+ * row and a NaN loss.  Fixed summation orders, no atomics.  rows == 0 returns 0 without a launch. */
+int k3m_cls_ce_fwd_bwd(float* z, long long ld, const long long* labels, const float* weight, float eps, int rows,
+                       int C, float* loss_rows, float* lse, float* loss, int* pred, float* denom, hipStream_t stream);
+int k3m_cls_ce_fwd(const float* z, long long ld, const long long* labels, const float* weight, float eps, int rows,
+                   int C, float* loss_rows, float* lse, float* loss, int* pred, float* denom, hipStream_t stream);
+
 /* ---- Top-k item retrieval over item embeddings ---------------------------------
  * For every row of Q [nq][h] the k best rows of the catalogue C [nc][h] (both fp32 row-major, 16-B aligned,
  * h % 4 == 0, 4 <= h <= 4096, 1 <= k <= 64) by inner product or cosine (norms clamped at 1e-8: a zero vector

@@ -124,6 +124,12 @@ SIGNATURES = {
     "k3m_align_cosine_fwd_bwd": [vp, vp, i32, i32, f32, vp, vp, vp, vp, vp],
     "k3m_align_ce_fwd": [vp, vp, vp, vp, i32, i32, f32, u64, u64, vp, vp, vp, vp, vp],
     "k3m_align_cosine_fwd": [vp, vp, i32, i32, f32, vp, vp, vp, vp],
+    "k3m_cls_drop_fwd": [vp, i32, i32, f32, u64, u64, vp, vp],
+    "k3m_cls_drop_bwd": [vp, i32, i32, f32, u64, u64, vp, vp],
+    "k3m_cls_tanh_drop_fwd": [vp, i32, i32, f32, u64, u64, vp, vp],
+    "k3m_cls_tanh_drop_bwd": [vp, vp, i32, i32, f32, u64, u64, vp, vp],
+    "k3m_cls_ce_fwd_bwd": [vp, i64, vp, vp, f32, i32, i32, vp, vp, vp, vp, vp, vp],
+    "k3m_cls_ce_fwd": [vp, i64, vp, vp, f32, i32, i32, vp, vp, vp, vp, vp, vp],
     "k3m_topk_sim_ws_bytes": [i32, i32, i32, i32, i32, vp],
     "k3m_topk_sim": [vp, vp, i32, i32, i32, i32, i32, i64, vp, i32, i32, vp, vp, vp, i64, vp],
     "k3m_topk_logits_ws_bytes": [i32, i32, i32, i32, i32, vp],

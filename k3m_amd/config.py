@@ -140,3 +140,20 @@ def finetune_config(path, loss_type="ce", use_image=True, with_coattention=True,
     cfg.task = "item_alignment"
     cfg.fixed_t_layer = fixed_t_layer   # finetune.py:1318-1319
     return cfg
+
+
+def classify_config(path, num_labels, use_image=True, with_coattention=True, if_pre_sampling=1,
+                    dynamic_attention=False, fixed_t_layer=0, label_smoothing=0.0):
+    """Item classification (the first downstream task of the K3M paper): finetune_config's mutations,
+    then task "item_classification" with ``num_labels`` categories and the cross entropy's ``label_smoothing``."""
+    if isinstance(num_labels, bool) or not isinstance(num_labels, int) or num_labels < 1:
+        raise ValueError("num_labels = %r: an int >= 1" % (num_labels,))
+    if not 0.0 <= float(label_smoothing) < 1.0:
+        raise ValueError("label_smoothing = %r: a number in [0, 1)" % (label_smoothing,))
+    cfg = finetune_config(path, loss_type="ce", use_image=use_image, with_coattention=with_coattention,
+                          if_pre_sampling=if_pre_sampling, dynamic_attention=dynamic_attention,
+                          fixed_t_layer=fixed_t_layer)
+    cfg.task = "item_classification"
+    cfg.num_labels = num_labels
+    cfg.label_smoothing = float(label_smoothing)
+    return cfg

@@ -485,3 +485,78 @@ class PairCollator(object):
             keep.append(hold)
         self._hold = keep          # staging buffers stay alive until the next call
         return out, ids[0], ids[1]
+
+
+# ------------------------------------------------------------------------------------------------
+# Item classification: single labelled items.  Every record carries a category (field 3, ``cate``);
+# LabelVocab turns the strings into class ids, ItemCollator collates K3MPreprocessBatch.prepare_item samples.
+
+class LabelVocab(object):
+    """Category string <-> class id: the sorted unique non-empty categories are 0 .. C-1; an empty or unseen
+    category encodes as -1 (unlabelled).  ``counts[c]``: the records of class c the vocabulary was built from."""
+
+    def __init__(self, names, counts=None):
+        self.names = [str(n) for n in names]
+        if len(set(self.names)) != len(self.names) or "" in self.names:
+            raise ValueError("LabelVocab: the names must be distinct and non-empty")
+        self.counts = [int(c) for c in counts] if counts is not None else [0] * len(self.names)
+        if len(self.counts) != len(self.names):
+            raise ValueError("LabelVocab: %d counts for %d names" % (len(self.counts), len(self.names)))
+        self._id = {n: i for i, n in enumerate(self.names)}
+
+    def __len__(self):
+        return len(self.names)
+
+    @classmethod
+    def from_records(cls, records):
+        seen = {}
+        for i in range(len(records)):
+            cate = str(records[i][3])
+            if cate:
+                seen[cate] = seen.get(cate, 0) + 1
+        names = sorted(seen)
+        return cls(names, [seen[n] for n in names])
+
+    def encode(self, cate):
+        return self._id.get(str(cate), -1)
+
+    def balanced_weights(self):
+        """float32 [C]: N / (C * n_c), the "balanced" class weights (N = the labelled records)."""
+        n = np.asarray(self.counts, np.float64)
+        if len(n) == 0 or (n <= 0).any():
+            raise ValueError("balanced_weights needs a positive count for every class")
+        return (n.sum() / (len(n) * n)).astype(np.float32)
+
+    def save(self, path):
+        import json
+        with open(path, "w", encoding="utf-8") as f:
+            json.dump({"names": self.names, "counts": self.counts}, f, ensure_ascii=False, indent=1)
+
+    @classmethod
+    def load(cls, path):
+        import json
+        with open(path, encoding="utf-8") as f:
+            d = json.load(f)
+        return cls(d["names"], d.get("counts"))
+
+
+class ItemCollator(object):
+    """Single labelled items -> the engine-named batch: ``(label, PreparedItem)`` samples (K3MPreprocessBatch.
+    prepare_item: nothing masked, nothing drawn) through the per-item GPU collation of PairCollator.  Returns
+    (batch with ``labels`` int64 [B] and ``image_target``, the item ids)."""
+
+    NAMES = (("input_ids", "input_ids"), ("token_type_ids", "segment_ids"), ("attention_mask", "input_mask"),
+             ("input_ids_pv", "input_ids_pv"), ("token_type_ids_pv", "segment_ids_pv"),
+             ("attention_mask_pv", "input_mask_pv"), ("index_p", "index_p"), ("index_v", "index_v"),
+             ("image_feat", "image_feat"), ("image_loc", "image_loc"), ("image_attention_mask", "image_mask"),
+             ("image_target", "image_target"))
+
+    def __init__(self, device, max_region_len=36, v_feature_size=2048, v_target_size=1601, visual_target=0):
+        self.pair = PairCollator(device, max_region_len, v_feature_size, v_target_size, visual_target)
+
+    def __call__(self, samples):
+        t = self.pair.torch
+        d, ids, self._hold = self.pair._item([s[1] for s in samples])   # staging stays alive until the next call
+        batch = {dst: d[src] for src, dst in self.NAMES}
+        batch["labels"] = t.from_numpy(np.array([int(s[0]) for s in samples], np.int64)).to(self.pair.device)
+        return batch, ids

@@ -321,3 +321,40 @@ class K3MDataLoader(object):
             pair, ids1, ids2 = self.collate([self.pre.prepare(self.records[i]) for i in order[s:s + self.batch_size]])
             pair["item_ids_1"], pair["item_ids_2"] = ids1, ids2
             yield pair
+
+
+# ---------------------------------------------------------------- item classification (single labelled items)
+class K3MItemLoader(object):
+    """Labelled single items for k3m_amd.classify: iterates device batches with the engine's field names, ``labels``
+    (int64, the record's category through ``vocab``; -1 for an empty or unseen one) and ``item_ids``.  records: any
+    sequence of 10-field records (open_records: a write_records directory or a raw product TSV).  Built on
+    K3MPreprocessBatch.prepare_item + ItemCollator (collation on the GPU); nothing is masked or drawn, ``seed``
+    orders the shuffle."""
+
+    def __init__(self, records, tokenizer, vocab, device=None, batch_size=32, shuffle=True, seed=None, max_seq_len=32,
+                 max_seq_len_pv=32, max_num_pv=20, max_region_len=36, v_feature_size=2048, v_target_size=1601,
+                 visual_target=0):
+        from .data import ItemCollator, K3MPreprocessBatch
+        self.records, self.vocab = records, vocab
+        self.num_dataset = len(records)
+        self.batch_size, self.shuffle = int(batch_size), shuffle
+        self._order_rng = random.Random(seed)
+        self.pre = K3MPreprocessBatch(tokenizer, max_seq_len=max_seq_len, max_seq_len_pv=max_seq_len_pv,
+                                      max_num_pv=max_num_pv, max_region_len=max_region_len,
+                                      v_feature_size=v_feature_size, v_target_size=v_target_size,
+                                      visual_target=visual_target)
+        self.collate = ItemCollator(_device_of(device, -1), max_region_len, v_feature_size, v_target_size,
+                                    visual_target)
+
+    def __len__(self):
+        return (self.num_dataset + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        order = list(range(self.num_dataset))
+        if self.shuffle:
+            self._order_rng.shuffle(order)
+        for s in range(0, len(order), self.batch_size):
+            recs = [self.records[i] for i in order[s:s + self.batch_size]]
+            batch, ids = self.collate([(self.vocab.encode(r[3]), self.pre.prepare_item(r)) for r in recs])
+            batch["item_ids"] = ids
+            yield batch

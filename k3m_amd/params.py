@@ -89,6 +89,8 @@ def param_spec(cfg):
     "item_alignment" (K3MForItemAlignment, vilbert_k3m.py:2862-2950)."""
     if getattr(cfg, "task", "pretrain") == "item_alignment":
         return item_alignment_spec(cfg)
+    if getattr(cfg, "task", "pretrain") == "item_classification":
+        return item_classification_spec(cfg)
     H, I, V = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size
     Hv, Iv, Hb = cfg.v_hidden_size, cfg.v_intermediate_size, cfg.bi_hidden_size
     use_image = getattr(cfg, "use_image", True)
@@ -192,6 +194,23 @@ def item_alignment_spec(cfg):
         s += _lin("classifier.dense", H, 2 * H) + _lin("classifier.out_proj", 2, H)
     s += _lin("struc_w1", H, 3 * H) + _lin("struc_w2", 1, H) + _lin("struc_w3", H, H)
     return s
+
+
+def item_classification_spec(cfg):
+    """The item-classification model (k3m_amd/classify.py): the tensors of item_alignment_spec with the "ce" head,
+    same names and order, the ClassificationHead reading ONE item's c_final: classifier.dense (H, H) and
+    classifier.out_proj (cfg.num_labels, H)."""
+    H, C = cfg.hidden_size, int(cfg.num_labels)
+    shapes = {"classifier.dense.weight": (H, H), "classifier.out_proj.weight": (C, H),
+              "classifier.out_proj.bias": (C,)}
+    return [(n, shapes.get(n, s)) for n, s in item_alignment_spec(_as_ce(cfg))]
+
+
+def _as_ce(cfg):
+    import copy
+    c = copy.copy(cfg)
+    c.loss_type = "ce"
+    return c
 
 
 _FROZEN_RE = re.compile(r"(\.q_dense[12]\.|^t_pooler\.|^v_pooler\.|^cls\.seq_relationship\.|"
