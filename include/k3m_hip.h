@@ -524,6 +524,26 @@ int k3m_topk_logits(const float* x, const float* w, const float* bias, int n, in
                     const long long* gold, int chunks, float* scores, long long* idx, float* lse, float* gold_score,
                     void* ws, long long ws_bytes, hipStream_t stream);
 
+/* ---- Link-prediction ranking: fused squared-L2 top-k and rank -------------------
+ * For every row of q [nq][h] and the candidates c [nc][h] (both fp32 row-major, 16-B aligned, h % 4 == 0,
+ * 4 <= h <= 4096, nc >= 1) the k nearest (farthest != 0: farthest) candidate rows by squared L2 distance
+ * (1 <= k <= 32: the per-lane list of a wider k spills, see §24.2) and the rank of one gold row over ALL
+ * eligible rows, fused: the score s = sign (2 q.c - |c|^2) comes out of exact-f32 MFMA accumulators and goes
+ * straight into a running top-k and an integer count, the [nq][nc] matrix is never stored.  Order, of the list and
+ * of the count alike: higher s first, equal s by ascending row.  d2 [nq][k] fp32 = max(|q|^2 - sign s, 0) /
+ * idx [nq][k] int64 = c_base + row; slots past the number of eligible rows hold (+inf, -1).  gold (int64 [nq], or
+ * NULL): a row of c or -1; gold_d2 [nq] = its d2 (+inf without one, also for a value outside [0, nc)); rank [nq]
+ * int64 = 1 + the number of eligible rows other than gold[i] that stand before it (0 without one).  The gold's
+ * score has the bits the tile kernel gives that pair, so a row bit-equal to the gold row ties with it.  q_gid
+ * (int64 [nq]) and c_gid (int64 [nc]), both or neither: row r is eligible for query i iff r == gold[i] or
+ * q_gid[i] < 0 or c_gid[r] != q_gid[i].  chunks: into how many pieces the candidates are split across workgroups
+ * (0 = choose); every output is bit-identical for every value and for both tilings.  ws: k3m_lp_rank_ws_bytes(...)
+ * bytes, 16-B aligned.  nq == 0 is a no-op.  No atomics. */
+int k3m_lp_rank_ws_bytes(int nq, int nc, int h, int k, int chunks, long long* bytes);
+int k3m_lp_rank(const float* q, const float* c, int nq, int nc, int h, int k, int farthest, long long c_base,
+                const long long* gold, const long long* q_gid, const long long* c_gid, int chunks, float* d2,
+                long long* idx, float* gold_d2, long long* rank, void* ws, long long ws_bytes, hipStream_t stream);
+
 /* ---- Data path ------------------------------------------------------
  * Global-region collation of a batch of region features, fused with mask_region's feature
  * zeroing: replaces the numpy block of ConceptCapLoaderTrain_struc.__iter__

@@ -134,6 +134,8 @@ SIGNATURES = {
     "k3m_topk_sim": [vp, vp, i32, i32, i32, i32, i32, i64, vp, i32, i32, vp, vp, vp, i64, vp],
     "k3m_topk_logits_ws_bytes": [i32, i32, i32, i32, i32, vp],
     "k3m_topk_logits": [vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, i64, vp],
+    "k3m_lp_rank_ws_bytes": [i32, i32, i32, i32, i32, vp],
+    "k3m_lp_rank": [vp, vp, i32, i32, i32, i32, i32, i64, vp, vp, vp, i32, vp, vp, vp, vp, vp, i64, vp],
 }
 
 _lib = None

@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libk3m_hip.so")
-SOURCES = ["gemm.hip", "gemm_x6p.hip", "gemm_bf16.hip", "norm.hip", "attention.hip", "attention_bf16.hip", "loss.hip", "fusion.hip", "struct.hip", "adamw.hip", "data.hip", "align.hip", "attention_long.hip", "attention_flash_long.hip", "dynattn.hip", "topk.hip", "topk_logits.hip", "classify.hip"]
+SOURCES = ["gemm.hip", "gemm_x6p.hip", "gemm_bf16.hip", "norm.hip", "attention.hip", "attention_bf16.hip", "loss.hip", "fusion.hip", "struct.hip", "adamw.hip", "data.hip", "align.hip", "attention_long.hip", "attention_flash_long.hip", "dynattn.hip", "topk.hip", "topk_logits.hip", "classify.hip", "lprank.hip"]
 # -fno-slp-vectorize: no packed-f32 (v_pk_*_f32) code from paired scalar math.  Beside MFMAs packed f32
 # VALU costs more than the scalar pair (MI355X_MICROARCH.md cycle constants), and in the GEMM epilogues
 # the packed alpha/beta form  v_pk_fma_f32 s[alpha:beta], op_sel  dropped the beta*C term for

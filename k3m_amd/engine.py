@@ -687,10 +687,11 @@ class K3MEngine(object):
                                    "collation, or a hand-built _label_counts)" % (hint, got))
 
     # ------------------------------------------------------------ stages of both steps (this one and engine_text's)
-    def _struct_fwd(self, ctx, batch, seq_tp, c_init, rng, ent_neg, val_neg, groups, save=True):
+    def _struct_fwd(self, ctx, batch, seq_tp, c_init, rng, ent_neg, val_neg, groups, save=True, keep=None):
         """Structure aggregator + LPM (:2413-2505) over the PV rows of seq_tp; returns (c_final, LPM loss), the loss
         None for a task other than pretraining (the encoder up to c_final only).  save=False (embed): the
-        aggregator alone for every task; ctx (B, T, P) is only read."""
+        aggregator alone for every task; ctx (B, T, P) is only read.  keep (a dict, with save=False: triples):
+        receives the gathered X [B NPV, 3 H] = [c_init | p | v] and nvalid [B] that embed discards."""
         c, fp, dev = self.cfg, self.fp, self.device
         B, T, P, H = ctx["B"], ctx["T"], ctx["P"], self.H
         BT = B * T
@@ -717,6 +718,8 @@ class K3MEngine(object):
         c_final = c_init.clone()
         self.sw3.fwd(agg, out=c_final, beta=1.0)
         if not save:
+            if keep is not None:
+                keep["X"], keep["nvalid"] = X, nvalid
             return c_final, None
         ctx["groups"] = groups
         ctx["batch"] = batch
@@ -1179,6 +1182,16 @@ class K3MEngine(object):
         ``noise``.  Works for both tasks (no head, no LPM, no label field read).  k3m_amd/infer.py."""
         from . import infer
         return infer.embed(self, batch, noise=noise, seed=seed, groups=groups)
+
+    def triples(self, batch, noise=None, seed=None, groups=1):
+        """The vectors the link-prediction objective ranks, forward-only: embed()'s path, which also
+        hands back the property and value means that the structure aggregator gathers (the p and v thirds of its X
+        buffer).  Returns {c_final [B, H], p [B, NPV, H], v [B, NPV, H], nvalid [B] int32}: triple j < nvalid[i] of
+        item i is (c_final[i], p[i, j], v[i, j]); rows past nvalid hold what the gather left there and are not
+        triples.  c_final has the bits of embed()'s.  Nothing is kept for a backward, fp.grad is untouched and a
+        pending forward's ctx is left alone.  k3m_amd/infer.py."""
+        from . import infer
+        return infer.triples(self, batch, noise=noise, seed=seed, groups=groups)
 
     def predict_masked(self, batch, k=10, rows="labels", noise=None, seed=None, mask_id=103):
         """What the model predicts at masked positions: the eval-mode, forward-only encoder and fusion

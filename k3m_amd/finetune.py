@@ -101,20 +101,27 @@ class K3MForItemAlignment(object):
         """K3MForItemAlignment.item_embedding (vilbert_k3m.py:3329-3377): (c_initial, c_final) of a batch of items
         through engine.embed (forward-only kernels, nothing kept for a backward).  The image arguments may be None
         without the image modality.  noise: optional {v,t,pv} gumbel-noise dict; seed: the draw's seed otherwise."""
+        out = self.engine.embed(self._item_batch(locals()), noise=noise, seed=seed)
+        return out["c_initial"], out["c_final"]
+
+    def _item_batch(self, given):
+        """item_embedding's arguments (by name) -> the engine's batch of single items"""
         eng = self.engine
-        given = {"input_ids": input_ids, "token_type_ids": token_type_ids, "attention_mask": attention_mask,
-                 "input_ids_pv": input_ids_pv, "token_type_ids_pv": token_type_ids_pv,
-                 "attention_mask_pv": attention_mask_pv, "index_p": index_p, "index_v": index_v,
-                 "image_feat": image_feat, "image_loc": image_loc, "image_attention_mask": image_attention_mask}
         batch = {}
         for src, dst in _ENGINE_NAMES:
             if not eng.use_image and _is_image_arg(src):
                 continue
-            if given[src] is None:
+            if given.get(src) is None:
                 raise TypeError("missing argument: %s" % src)
             batch[dst] = given[src].to(eng.device).contiguous()
-        out = eng.embed(batch, noise=noise, seed=seed)
-        return out["c_initial"], out["c_final"]
+        return batch
+
+    def triples(self, input_ids, image_feat=None, image_loc=None, token_type_ids=None, attention_mask=None,
+                image_attention_mask=None, input_ids_pv=None, token_type_ids_pv=None, attention_mask_pv=None,
+                index_p=None, index_v=None, noise=None, seed=None, groups=1):
+        """The link-prediction vectors of a batch of items (K3MEngine.triples): item_embedding's arguments; returns
+        {c_final, p, v, nvalid}."""
+        return self.engine.triples(self._item_batch(locals()), noise=noise, seed=seed, groups=groups)
 
     def predict(self, *args, output_all_attention_masks=False, noise=None, seed=None, embeddings=False, **kw):
         """forward's arguments and 4-tuple in eval mode, through engine.embed(groups=2) and the forward-only pair

@@ -166,10 +166,10 @@ def sequences(eng, batch, noise=None, seed=None):
     return seq_tp, seq_v, rng
 
 
-def embed(eng, batch, noise=None, seed=None, groups=1):
-    """K3MEngine.embed; see there."""
+def embed(eng, batch, noise=None, seed=None, groups=1, keep=None):
+    """K3MEngine.embed; see there.  keep: _struct_fwd's (triples)."""
     if not eng.use_image:
-        return _embed_text(eng, batch, noise, seed, groups)
+        return _embed_text(eng, batch, noise, seed, groups, keep)
     dev, H, Hv = eng.device, eng.H, eng.Hv
     seq_tp, seq_v, rng = sequences(eng, batch, noise, seed)
     B, T = batch["input_ids"].shape
@@ -186,9 +186,22 @@ def embed(eng, batch, noise=None, seed=None, groups=1):
     c_init = torch.empty((B, H), **f32)
     L.call("k3m_mean3", pooled_v.data_ptr(), pooled_t.data_ptr(), pooled_pv.data_ptr(), c_init.data_ptr(),
            c_init.numel(), L.F32, L.stream())
-    c_final, _ = eng._struct_fwd({"B": B, "T": T, "P": P}, batch, seq_tp, c_init, rng, None, None, groups, save=False)
+    c_final, _ = eng._struct_fwd({"B": B, "T": T, "P": P}, batch, seq_tp, c_init, rng, None, None, groups, save=False,
+                                 keep=keep)
     return {"c_initial": c_init, "c_final": c_final, "pooled_t": pooled_t, "pooled_pv": pooled_pv,
             "pooled_v": pooled_v}
+
+
+def triples(eng, batch, noise=None, seed=None, groups=1):
+    """K3MEngine.triples; see there.  embed() with the structure aggregator's gathered rows kept: p and v are
+    views of the thirds of X [B NPV, 3 H] = [c_init | p | v]."""
+    keep = {}
+    out = embed(eng, batch, noise=noise, seed=seed, groups=groups, keep=keep)
+    H = eng.H
+    X = keep["X"]
+    B = out["c_final"].shape[0]
+    X3 = X.view(B, X.shape[0] // B, 3 * H)
+    return {"c_final": out["c_final"], "p": X3[:, :, H:2 * H], "v": X3[:, :, 2 * H:], "nvalid": keep["nvalid"]}
 
 
 def _sequences_text(eng, batch, noise, seed):
@@ -236,7 +249,7 @@ def _sequences_text(eng, batch, noise, seed):
     return seq_tp, None, rng
 
 
-def _embed_text(eng, batch, noise, seed, groups):
+def _embed_text(eng, batch, noise, seed, groups, keep=None):
     """embed() of the model without the image modality."""
     dev, H = eng.device, eng.H
     seq_tp, _, rng = _sequences_text(eng, batch, noise, seed)
@@ -250,5 +263,6 @@ def _embed_text(eng, batch, noise, seed, groups):
     L.call("k3m_seq_mean", seq_tp[BT:].data_ptr(), B, P, 1, H, 1.0, pooled_pv.data_ptr(), 0, L.F32, L.stream())
     c_init = torch.empty((B, H), **f32)
     L.call("k3m_mean2", pooled_t.data_ptr(), pooled_pv.data_ptr(), c_init.data_ptr(), c_init.numel(), L.F32, L.stream())
-    c_final, _ = eng._struct_fwd({"B": B, "T": T, "P": P}, batch, seq_tp, c_init, rng, None, None, groups, save=False)
+    c_final, _ = eng._struct_fwd({"B": B, "T": T, "P": P}, batch, seq_tp, c_init, rng, None, None, groups, save=False,
+                                 keep=keep)
     return {"c_initial": c_init, "c_final": c_final, "pooled_t": pooled_t, "pooled_pv": pooled_pv, "pooled_v": None}

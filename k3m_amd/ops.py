@@ -827,3 +827,61 @@ def topk_logits(x, W, bias=None, k=10, gold=None, chunks=0):
     call("k3m_topk_logits", ptr(x), ptr(W), ptr(bias), n, v, H, k, ptr(gold), chunks, ptr(scores), ptr(idx), ptr(lse),
          ptr(gs), ptr(ws), int(nb.value), stream())
     return scores, idx, lse, gs
+
+
+# ------------------------------------------------------------------ link-prediction ranking (lprank.hip)
+LP_RANK_MAX_K = 32
+
+
+def lp_rank(q, c, gold=None, k=10, q_gid=None, c_gid=None, farthest=False, c_base=0, chunks=0):
+    """(d2 [Nq, k] fp32, idx [Nq, k] int64, gold_d2 [Nq] fp32, rank [Nq] int64): for every row of q [Nq, H] the k
+    nearest (farthest=True: farthest) rows of the candidates c [Nc, H] (fp32, contiguous) by squared L2 distance,
+    and the rank of the row gold[i] (int64 [Nq]; -1: none) over ALL eligible candidates, fused: the [Nq, Nc]
+    distances are never stored.  Rows are listed and counted in one strict order: nearer (farther)
+    first, equal scores by ascending index.  rank[i] = 1 + the number of eligible rows other than gold[i] before it
+    (0 without a gold), gold_d2[i] = its squared distance (+inf without one); idx = c_base + candidate row; slots
+    past the number of eligible rows hold (+inf, -1).  q_gid [Nq] / c_gid [Nc] (int64, both or neither): row r is
+    eligible for query i iff r == gold[i] or q_gid[i] < 0 or c_gid[r] != q_gid[i] (the filtered setting).  chunks:
+    the number of candidate pieces dealt to workgroups (0: chosen from the shapes); every value gives the same
+    bits.  Every argument is checked here, before any library call (ValueError)."""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= LP_RANK_MAX_K:
+        raise ValueError("k = %r: an int in [1, %d]" % (k, LP_RANK_MAX_K))
+    for name, t in (("q", q), ("c", c)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError("%s: a 2-D tensor [rows, H] expected" % name)
+        if t.dtype != torch.float32:
+            raise ValueError("%s: dtype %s, float32 expected" % (name, t.dtype))
+        if not t.is_contiguous():
+            raise ValueError("%s: contiguous rows expected" % name)
+    if q.shape[1] != c.shape[1]:
+        raise ValueError("H differs: q has %d columns, c has %d" % (q.shape[1], c.shape[1]))
+    H = q.shape[1]
+    if H % 4 != 0 or not 4 <= H <= 4096:
+        raise ValueError("H = %d: a multiple of 4 in [4, 4096]" % H)
+    if q.device != c.device:
+        raise ValueError("q and c are on different devices")
+    if isinstance(chunks, bool) or not isinstance(chunks, int) or chunks < 0:
+        raise ValueError("chunks = %r: an int >= 0" % (chunks,))
+    if isinstance(c_base, bool) or not isinstance(c_base, int):
+        raise ValueError("c_base = %r: an int" % (c_base,))
+    if not isinstance(farthest, bool):
+        raise ValueError("farthest = %r: a bool" % (farthest,))
+    nq, nc = q.shape[0], c.shape[0]
+    if nc < 1 or nq >= 2 ** 31 or nc >= 2 ** 31:
+        raise ValueError("1 <= Nc and at most 2^31 - 1 rows per call")
+    for name, t, n in (("gold", gold, nq), ("q_gid", q_gid, nq), ("c_gid", c_gid, nc)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.shape != (n,)
+                              or not t.is_contiguous() or t.device != q.device):
+            raise ValueError("%s: a contiguous int64 [%d] tensor on q's device expected" % (name, n))
+    if (q_gid is None) != (c_gid is None):
+        raise ValueError("q_gid and c_gid: both or neither")
+    d2 = empty((nq, k), q)
+    idx = empty((nq, k), q, dtype=torch.int64)
+    gold_d2 = empty((nq,), q)
+    rank = empty((nq,), q, dtype=torch.int64)
+    nb = C.c_longlong(0)
+    call("k3m_lp_rank_ws_bytes", nq, nc, H, k, chunks, C.addressof(nb))
+    ws = torch.empty((max(int(nb.value), 16),), dtype=torch.uint8, device=q.device)
+    call("k3m_lp_rank", ptr(q), ptr(c), nq, nc, H, k, int(farthest), c_base, ptr(gold), ptr(q_gid), ptr(c_gid), chunks,
+         ptr(d2), ptr(idx), ptr(gold_d2), ptr(rank), ptr(ws), int(nb.value), stream())
+    return d2, idx, gold_d2, rank

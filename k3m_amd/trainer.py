@@ -254,6 +254,10 @@ class Trainer(object):
         """K3MEngine.predict_masked on a validation batch (k, rows, noise, seed, mask_id pass through)."""
         return self.engine.predict_masked(batch, **kw)
 
+    def triples(self, batch, **kw):
+        """K3MEngine.triples on a validation batch (noise, seed, groups pass through)."""
+        return self.engine.triples(batch, **kw)
+
     # ---------------------------------------------------------------- schedule
     def current_lr(self):
         """lr of the next optimizer step for a multiplier-1 tensor of the first group."""

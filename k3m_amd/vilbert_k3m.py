@@ -197,14 +197,10 @@ class BertForMultiModalPreTraining_tri_stru(nn.Module):
         mlm_t, img, mlm_pv, nsp, c_init, c_final, lpm = _Step.apply(self._anchor, self, batch, kw)
         return (mlm_t, img, 0, mlm_pv, 0, 0, nsp, c_init, c_final, lpm)
 
-    def predict_masked(self, input_ids, image_feat=None, image_loc=None, token_type_ids=None, attention_mask=None,
-                       image_attention_mask=None, masked_lm_labels=None, image_label=None, image_target=None,
-                       input_ids_pv=None, token_type_ids_pv=None, attention_mask_pv=None, masked_lm_labels_pv=None,
-                       index_p=None, index_v=None, gumbel_noise=None, k=10, rows="labels", noise=None, seed=None,
-                       mask_id=103):
-        """What the model predicts at masked positions (K3MEngine.predict_masked): forward()'s argument names, the
-        label arguments optional (rows="labels" needs them; rows="mask" and explicit positions do not).  noise is
-        gumbel_noise under the engine's name; either may be given."""
+    def _eval_batch(self, input_ids, image_feat, image_loc, token_type_ids, attention_mask, image_attention_mask,
+                    input_ids_pv, token_type_ids_pv, attention_mask_pv, index_p, index_v, **optional):
+        """The engine's batch from forward()'s argument names, on the engine's device: absent masks are all ones,
+        absent segment ids zeros; optional (label fields under the engine's names) enter where given."""
         dev = self.engine.device
 
         def d(t, like=None):
@@ -222,10 +218,33 @@ class BertForMultiModalPreTraining_tri_stru(nn.Module):
             B, R = batch["image_feat"].shape[:2]
             batch["image_mask"] = (d(image_attention_mask) if image_attention_mask is not None
                                    else torch.ones((B, R), dtype=torch.int64, device=dev))
-        optional = dict(lm_label_ids=masked_lm_labels, lm_label_ids_pv=masked_lm_labels_pv, image_label=image_label,
-                        image_target=image_target)
         for name, t in optional.items():
             if t is not None:
                 batch[name] = d(t).float() if name == "image_target" else d(t)
+        return batch
+
+    def predict_masked(self, input_ids, image_feat=None, image_loc=None, token_type_ids=None, attention_mask=None,
+                       image_attention_mask=None, masked_lm_labels=None, image_label=None, image_target=None,
+                       input_ids_pv=None, token_type_ids_pv=None, attention_mask_pv=None, masked_lm_labels_pv=None,
+                       index_p=None, index_v=None, gumbel_noise=None, k=10, rows="labels", noise=None, seed=None,
+                       mask_id=103):
+        """What the model predicts at masked positions (K3MEngine.predict_masked): forward()'s argument names, the
+        label arguments optional (rows="labels" needs them; rows="mask" and explicit positions do not).  noise is
+        gumbel_noise under the engine's name; either may be given."""
+        batch = self._eval_batch(input_ids, image_feat, image_loc, token_type_ids, attention_mask,
+                                 image_attention_mask, input_ids_pv, token_type_ids_pv, attention_mask_pv, index_p,
+                                 index_v, lm_label_ids=masked_lm_labels, lm_label_ids_pv=masked_lm_labels_pv,
+                                 image_label=image_label, image_target=image_target)
         return self.engine.predict_masked(batch, k=k, rows=rows, noise=noise if noise is not None else gumbel_noise,
                                           seed=seed, mask_id=mask_id)
+
+    def triples(self, input_ids, image_feat=None, image_loc=None, token_type_ids=None, attention_mask=None,
+                image_attention_mask=None, input_ids_pv=None, token_type_ids_pv=None, attention_mask_pv=None,
+                index_p=None, index_v=None, gumbel_noise=None, noise=None, seed=None, groups=1):
+        """The link-prediction vectors of a batch (K3MEngine.triples): forward()'s argument names, no label read.
+        Returns {c_final, p, v, nvalid}.  noise is gumbel_noise under the engine's name; either may be given."""
+        batch = self._eval_batch(input_ids, image_feat, image_loc, token_type_ids, attention_mask,
+                                 image_attention_mask, input_ids_pv, token_type_ids_pv, attention_mask_pv, index_p,
+                                 index_v)
+        return self.engine.triples(batch, noise=noise if noise is not None else gumbel_noise, seed=seed,
+                                   groups=groups)

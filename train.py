@@ -22,7 +22,11 @@ Differences, each stated:
   ``--k3m_max_steps N``, ``--k3m_loss_log PATH`` (one JSON line per step), ``--k3m_eval_topk K`` with
   ``--do_eval`` (after the validation losses: what the model predicts at the masked positions of the validation
   set, logged as title / PV / region accuracy@1/5/K and gold NLL; ``--k3m_pred_output PATH`` also writes one JSON
-  line per predicted position), and the parity harness
+  line per predicted position), ``--k3m_eval_lpm K`` with ``--do_eval`` (after the validation losses,
+  on the same batches: the link-prediction objective as rankings over the validation set's triples, logged as
+  value / entity mean rank, MRR, Hits@1/3/K and the mean gold distance beside the mean distance of the rank-1
+  neighbour; ``--k3m_lpm_output PATH`` also writes one JSON line per triple, ``--k3m_lpm_farthest`` ranks farthest
+  first), and the parity harness
   ``--k3m_parity_case NPZ``: every step feeds the fixture's recorded batch with its gumbel noise and LPM
   negatives, dropout off (the golden vectors were recorded with model.eval(); tests/test_gpu_train_driver.py);
 * ``--text_only``: the model without the image modality (``config.use_image = False``, the reference's
@@ -106,6 +110,14 @@ def get_parser(argv=None):
                         "region accuracy@1/5/K and the gold NLL (0: off)")
     p.add_argument("--k3m_pred_output", default="", type=str,
                    help="with --k3m_eval_topk: write one JSON line per predicted position to this file")
+    p.add_argument("--k3m_eval_lpm", default=0, type=int,
+                   help="with --do_eval: also rank the validation set's triples (value and entity link prediction) "
+                        "and log MR / MRR / Hits@1/3/K (0: off)")
+    p.add_argument("--k3m_lpm_output", default="", type=str,
+                   help="with --k3m_eval_lpm: write one JSON line per triple to this file")
+    p.add_argument("--k3m_lpm_farthest", action="store_true",
+                   help="with --k3m_eval_lpm: rank farthest first (a model trained with the reference's LPM loss sign "
+                        "pushes true triples apart)")
     p.add_argument("--text_only", action="store_true",
                    help="train the model without the image modality (config.use_image = False): title + "
                         "property-value knowledge only; the loaders' image fields are ignored")
@@ -312,6 +324,11 @@ def main(argv=None):
             if args.k3m_eval_topk:
                 from k3m_amd.predict import MaskedEval, STREAM_NAMES
                 pred = MaskedEval(args.k3m_eval_topk, args.k3m_pred_output if default_gpu else "")
+            link = None
+            if args.k3m_eval_lpm:
+                from k3m_amd.linkpred import LinkEval
+                link = LinkEval(args.k3m_eval_lpm, args.k3m_lpm_output if default_gpu else "",
+                                farthest=args.k3m_lpm_farthest)
             for step, (batch, _ids) in enumerate(valid_loader.batches()):
                 out = trainer.evaluate(batch)
                 logger.info(f"[Eval] [Epoch-{epoch}] loss: {_trunc(out['loss'])} "
@@ -320,12 +337,22 @@ def main(argv=None):
                             f"loss_pv: {_trunc(out['masked_lm_loss_pv'])}, loss_tri: {_trunc(out['loss_lpm'])}")
                 if pred is not None:
                     pred.add(trainer.predict_masked(batch, k=args.k3m_eval_topk), _ids)
+                if link is not None:
+                    link.add(trainer, batch, _ids)
             if pred is not None:
                 pred.close()
                 for name, m in pred.summary().items():
                     accs = " ".join(f"acc@{kk}: {_trunc(m['acc@%d' % kk])}" for kk in pred.ks)
                     logger.info(f"[Eval] [Epoch-{epoch}] {STREAM_NAMES[name]} {accs} nll: {_trunc(m['nll'])} "
                                 f"rows: {m['n']}")
+            if link is not None:
+                link.close()
+                for name, m in link.summary().items():
+                    hits = " ".join(f"hits@{kk}: {_trunc(m['hits@%d' % kk])}" for kk in link.ks)
+                    logger.info(f"[Eval] [Epoch-{epoch}] {name} mr: {_trunc(m['mr'])} mrr: {_trunc(m['mrr'])} {hits} "
+                                f"n: {m['n']}")
+                    logger.info(f"[Eval] [Epoch-{epoch}] {name} gold distance: {_trunc(m['gold_dist'])} "
+                                f"rank-1 distance: {_trunc(m['top1_dist'])} n: {m['n']}")
         if default_gpu:
             logger.info(f"[Epoch-{epoch}] saving model")
             base = os.path.join(output_model_path, f"K3M_struc_presample-{args.if_pre_sampling}_epoch-{epoch}")
